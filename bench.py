@@ -3,6 +3,13 @@
 
     python bench.py [--gpus N --steps K --warmup W]     (N > 1 without a launcher: re-launches itself under
                                                          torch.distributed.run before anything touches a GPU)
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, makes the first call, warms up, times the K steps and prints the line.  `--dump-outputs DIR` writes what the
+last timed step computed (the four edited fc2 weights, float32 .npy; the inputs are seeded, so two builds compare output for
+output).  `--full` adds the other records described below: the replay / new-weight calls, the GEMM A/B, the host/device split, the roofline
+pass, the secondary records, the CPU baseline and Stage 0 (the --no-* switches leave parts of it out); with N > 1 also
+`per_rank` and `weak_replicas`.
 
 Workload (config.workload): the 1 000-concept batch on SD-v1.4 dims the metric is quoted on — CLIP ViT-L/14 text
 encoder (768 / 3072 / 12 layers, random init), layers [7, 8, 9, 10], lambda = 4000, edit_weight 0.5, 3 prompts per
@@ -82,10 +89,11 @@ def request_set(n_concepts, workdir, index=0, write=True):
     return reqs, cache
 
 
-def build_inputs(n_concepts, device, workdir):
+def write_inputs(n_concepts, workdir):
+    """Request set 0 with its v* files and the statistics files of the edited layers (written once per workdir).
+    Returns (requests, cache, hparams dict, stats dir, layer names)."""
     from emcid_amd import synthetic as syn
 
-    pipe = syn.build_pipe(KIND, device, syllables=True)
     inter = syn.ENCODER_DIMS[KIND][1]
     hp_d = syn.sd_hparams_dict(layers=LAYERS, mom2_update_weight=LAM, edit_weight=EW)
     reqs, cache = request_set(n_concepts, workdir, 0)
@@ -94,7 +102,29 @@ def build_inputs(n_concepts, device, workdir):
     if not (stats / ".complete").exists():
         syn.write_stats_cache(stats, layer_names, inter, hp_d["mom2_n_samples"], seed=2, t=2 * inter)
         (stats / ".complete").touch()
-    return pipe, reqs, hp_d, cache, str(stats), layer_names
+    return reqs, cache, hp_d, str(stats), layer_names
+
+
+def build_inputs(n_concepts, device, workdir):
+    from emcid_amd import synthetic as syn
+
+    pipe = syn.build_pipe(KIND, device, syllables=True)
+    reqs, cache, hp_d, stats, layer_names = write_inputs(n_concepts, workdir)
+    return pipe, reqs, hp_d, cache, stats, layer_names
+
+
+def dump_outputs(out_dir, pipe, layer_names):
+    """What the caller of the timed path receives from its last step: the edited fc2 weights (the only parameters the call
+    changes), one float32 .npy per weight (4 x 768 x 3072 x 4 B = 38 MB)."""
+    import numpy as np
+    import torch
+    from emcid_amd.nethook import get_parameter
+
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for n in layer_names:
+        w = get_parameter(pipe.text_encoder, n + ".weight").detach().to("cpu", torch.float32).numpy()
+        np.save(out / f"{n}.weight.npy", w)
 
 
 def self_launch(args):
@@ -220,6 +250,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--concepts", type=int, default=1000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the edited fc2 weights) as DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: replay / new-weight calls, GEMM A/B, host/device split, roofline, "
+                         "the secondary records, the CPU baseline, Stage 0 (the --no-* switches below act inside it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-stage0", action="store_true")
     ap.add_argument("--gc-freeze", action="store_true", help="gc.freeze() once the inputs exist (default: the collector as it is)")
@@ -231,6 +266,8 @@ def main():
     ap.add_argument("--cold-child", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--stage0-captions", type=int, default=100000)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.cold_child:
         return cold_child(args.cold_child, args.concepts)
@@ -271,7 +308,7 @@ def main():
     n_sets = min(MAX_REQUEST_SETS, 1 + args.warmup + args.steps)      # set 0: the first call; then one per warm-up / timed step
     if rank == 0:
         workdir.mkdir(exist_ok=True, mode=0o700)
-        build_inputs(args.concepts, "cpu", workdir)     # writes the synthetic v*/stats caches once
+        write_inputs(args.concepts, workdir)            # writes the synthetic v*/stats caches once
         for j in range(1, n_sets):
             request_set(args.concepts, workdir, j)
     if world > 1:
@@ -380,11 +417,15 @@ def main():
                    "longest_ms": round(max((ms for _, ms in gc_events), default=0.0), 3)}
     slowest = slowest_call(per_call, list(call_marks), 1 + args.warmup)
     host_phases = {k: round(v / args.steps * 1e3, 4) for k, v in edit_engine.TIMING.items()}      # host wall-clock per phase and call
+    last_paths = dict(clip_forward.LAST_PATHS)       # the path counters and trie gauges as the timed steps left them
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pipe, layer_names)      # before any other call touches the weights
     per_rank = None
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         rank_elapsed, elapsed = elapsed, float(tmax.item())
+    if world > 1 and args.full:
         # per-rank phase times (a few more calls OUTSIDE the timed region, with event brackets around the collectives and the
         # solves): what a scaling curve is read with
         try:
@@ -398,7 +439,7 @@ def main():
     # edit), beside the strong-scaling number above (ONE list cut across the ranks, whose replicated N x N chain and per-layer
     # all-reduces do not divide) -------------------------------------------------------------------------------------------
     weak = None
-    if world > 1:
+    if world > 1 and args.full:
         try:
             solo = ConceptShard(0, 1, None)
 
@@ -423,6 +464,48 @@ def main():
         except Exception as e:         # diagnostics must never cost the line
             weak = {"error": repr(e)}
 
+    # ---- the headline line: what the timed steps themselves measured -------------------------------------------------------
+    own_gemm = bool(clip_forward.OWN_GEMM)
+    split_gemm = own_gemm and bool(clip_forward.SPLIT_GEMM)
+    fresh_ms = statistics.median(per_call) * 1e3
+    out = {
+        "metric": "concept-edits/sec (1 000-concept batch, SD-v1.4)", "value": value, "unit": "concept-edits/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": ("f32 forward (2 x fp16 split MFMA, fp32 accumulate) + f64 solve" if split_gemm else "f32 forward + f64 solve"), "data": "synthetic",
+        "config": {"workload": f"{args.concepts}-concept edit, SD-v1.4 text-encoder dims (768/3072/12L), layers 7-10, "
+                               f"lambda 4000, 3 prompts/concept; one step = one apply_emcid_to_text_encoder call, timer "
+                               f"around the call (v* npz on disk, C_l in the covariance cache, model in HBM); every step "
+                               f"edits a request set the process has not seen before",
+                   "concepts": args.concepts,
+                   "request_sets": {"distinct": len(sets), "used_by_first_warmup_timed": 1 + args.warmup + args.steps,
+                                    "note": "set i = 1 000 other syllable names + its own directory of 1 000 v* npz files; "
+                                            "cycled when warmup + steps exceed the distinct sets"},
+                   "forward": ("prefix-trie: %d unique rows of %d tokens (last timed step)"
+                               % (last_paths["last_trie_rows"], last_paths["last_trie_tokens"]))
+                   if "last_trie_rows" in last_paths else "hooked HF forward",
+                   "caches": {"covariance_in_hbm": True,
+                              "vstar_files": "read from the files in every call (native batch reader, no in-process copy)",
+                              "gemm_selection": "none needed (own GEMM)" if own_gemm else "torch F.linear, library-default selection"},
+                   "backend": (dist.get_backend() if world > 1 else None),
+                   "world_size_seen": (dist.get_world_size() if world > 1 else 1),
+                   "parallelism": f"concept-shard x{world}"},
+        "ms_per_call_median": fresh_ms,
+        "ms_per_call_min": min(per_call) * 1e3,
+        "ms_per_call": [round(t * 1e3, 3) for t in per_call],
+        "fresh_requests_ms": fresh_ms,                   # = the timed steps themselves
+        "first_call_ms": first_s * 1e3,
+        "host_phases_ms_per_call": host_phases, "slowest_call": slowest, "gc_in_timed_region": gc_in_timed, "cpu_throttle_in_timed_region": cpu_throttle,
+        "outputs_dumped_to": args.dump_outputs,
+        "full": bool(args.full),
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     # ---- the same 1 000 requests again and again (what rounds 1-2 reported as the step) ------------------------------------
     log(f"{elapsed / args.steps * 1e3:.2f} ms per step; replay / new-weight variants")
     call(0)
@@ -439,9 +522,6 @@ def main():
     log("GEMM A/B, host/device split, roofline pass")
     # ---- the forward's projections on torch's F.linear (hipBLASLt, library-default selection, element-wise passes unfused)
     # instead of the library's own fp32-MFMA GEMM with fused epilogues (csrc/gemm_f32.hip): a few calls -----------------------
-    from emcid_amd import clip_forward
-    own_gemm = bool(clip_forward.OWN_GEMM)
-    split_gemm = own_gemm and bool(clip_forward.SPLIT_GEMM)
     other_gemm_ms = None
     if not args.no_gemm_ab:
         # the A/B path: the exact-f32 MFMA kernel (csrc/gemm_f32.hip) when this run is on the split-fp16 kernel, else torch
@@ -607,34 +687,13 @@ def main():
                     "solver": "dual" if dual else "direct"}
 
     replay_ms = statistics.median(replay_per) * 1e3
-    fresh_ms = statistics.median(per_call) * 1e3
-    out = {
-        "metric": "concept-edits/sec (1 000-concept batch, SD-v1.4)", "value": value, "unit": "concept-edits/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "dtype": ("f32 forward (2 x fp16 split MFMA, fp32 accumulate) + f64 solve" if split_gemm else "f32 forward + f64 solve"), "data": "synthetic",
-        "config": {"workload": f"{args.concepts}-concept edit, SD-v1.4 text-encoder dims (768/3072/12L), layers 7-10, "
-                               f"lambda 4000, 3 prompts/concept; one step = one apply_emcid_to_text_encoder call, timer "
-                               f"around the call (v* npz on disk, C_l in the covariance cache, model in HBM); every step "
-                               f"edits a request set the process has not seen before",
-                   "concepts": args.concepts, "prompts_per_rank": plan.n_prompts,
-                   "request_sets": {"distinct": len(sets), "used_by_first_warmup_timed": 1 + args.warmup + args.steps,
-                                    "note": "set i = 1 000 other syllable names + its own directory of 1 000 v* npz files; "
-                                            "cycled when warmup + steps exceed the distinct sets"},
-                   "forward": ("prefix-trie: %d unique rows of %d tokens in %d slice(s)" % (*plan.trie_rows, len(plan.chunks)))
-                   if plan.chunks is not None else "hooked HF forward",
-                   "caches": {"covariance_in_hbm": True,
-                              "cov_factor_cache": ("warm (keyed by statistics + edit_weight; any mom2_update_weight)"
-                                                   if plan.factors_from_cache else "off"),
-                              "vstar_files": "read from the files in every call (native batch reader, no in-process copy)",
-                              "gemm_selection": "none needed (own GEMM)" if own_gemm else "torch F.linear, library-default selection"},
-                   "backend": (dist.get_backend() if world > 1 else None),
-                   "world_size_seen": (dist.get_world_size() if world > 1 else 1),
-                   "parallelism": f"concept-shard x{world}"},
-        "ms_per_call_median": fresh_ms,
-        "ms_per_call_min": min(per_call) * 1e3,
-        "ms_per_call": [round(t * 1e3, 3) for t in per_call],
-        "fresh_requests_ms": fresh_ms,                   # = the timed steps themselves
+    out["config"].update(
+        prompts_per_rank=plan.n_prompts,
+        forward=("prefix-trie: %d unique rows of %d tokens in %d slice(s)" % (*plan.trie_rows, len(plan.chunks)))
+        if plan.chunks is not None else "hooked HF forward")
+    out["config"]["caches"]["cov_factor_cache"] = ("warm (keyed by statistics + edit_weight; any mom2_update_weight)"
+                                                   if plan.factors_from_cache else "off")
+    out.update({
         "replay_ms_per_call": replay_ms, "replay_ms_per_call_all": [round(t * 1e3, 3) for t in replay_per],
         "fresh_over_replay": fresh_ms / replay_ms,
         "new_weights_ms": {"new_lambda_ms_per_call": statistics.median(new_lam_ms), "lambdas": lam_list,
@@ -643,8 +702,6 @@ def main():
                            "new_edit_weight_ms_all": [round(t, 3) for t in new_ew_ms],
                            "note": "same requests as the replay; a new lambda reuses the cached factor of C' (lam_ratio), a new "
                                    "edit_weight refactors the four 3072 x 3072 matrices on the side stream under the forward"},
-        "first_call_ms": first_s * 1e3,
-        "host_phases_ms_per_call": host_phases, "slowest_call": slowest, "gc_in_timed_region": gc_in_timed, "cpu_throttle_in_timed_region": cpu_throttle,
         "forward_gemm": {"this_run": ("emcid_linear_sp16_f32 (split-fp16 MFMA GEMM at fp32 accuracy, fused bias / activation / residual, "
                                        "native layer runner)" if split_gemm else
                                        "emcid_linear_f32 (own fp32-MFMA GEMM, fused bias / activation / residual)") if own_gemm
@@ -662,7 +719,7 @@ def main():
         "kernel_classes": classes,
         "per_rank": per_rank,
         "weak_replicas": weak,
-    }
+    })
 
     if rank == 0 and world == 1 and not args.no_variants:
         log("secondary records: n100, latency, realistic_names, n1500, no_shared_prefix, sdxl, stage1, cold_process")

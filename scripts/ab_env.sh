@@ -2,10 +2,10 @@
 # A/B of one environment switch on the bench: scripts/ab_env.sh NAME VAR=VALUE_A VAR=VALUE_B [bench args...]
 # Runs bench.py alternately (A, B, A, B) and prints value / ms_per_step / device_ms_per_step / chol classes of each run.
 name=$1; a=$2; b=$3; shift 3
-out=gpurun_out/$name; mkdir -p "$out"
+out=${OUT:-bench_out}/$name; mkdir -p "$out"
 for i in 1 2; do
-  env "$a" python bench.py "$@" > "$out/a$i.json" 2> "$out/a$i.err"
-  env "$b" python bench.py "$@" > "$out/b$i.json" 2> "$out/b$i.err"
+  env "$a" python bench.py --full "$@" > "$out/a$i.json" 2> "$out/a$i.err"
+  env "$b" python bench.py --full "$@" > "$out/b$i.json" 2> "$out/b$i.err"
 done
 python - "$out" "$a" "$b" <<'PY'
 import json, sys

@@ -3,11 +3,11 @@
 set -o pipefail
 tag=${1:-r03_a}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out
-python bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err && echo bench ok
-rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${tag}_prof -- python3 bench.py --no-cpu-baseline --no-stage0 --no-variants --no-gemm-ab > gpurun_out/${tag}_bench_under_rocprof.json 2> gpurun_out/${tag}_prof.err && echo prof ok
-f=$(find gpurun_out/${tag}_prof -name "*kernel_stats.csv" | head -1); cp "$f" gpurun_out/${tag}_bench_kernel_stats.csv; rm -rf gpurun_out/${tag}_prof
-bash scripts/pmc_passes.sh gpurun_out/${tag}_pmc_lin scripts/pmc_linear.py > gpurun_out/${tag}_pmc_linear_summary.json 2> gpurun_out/${tag}_pmc_lin.err && echo pmc linear ok
-find gpurun_out/${tag}_pmc_lin -name "*.csv" -delete; find gpurun_out/${tag}_pmc_lin -type d -empty -delete
-bash scripts/pmc_passes.sh gpurun_out/${tag}_pmc scripts/pmc_edit_steps.py 4 > gpurun_out/${tag}_pmc_edit_summary.json 2> gpurun_out/${tag}_pmc.err && echo pmc edit ok
-find gpurun_out/${tag}_pmc -name "*.csv" -delete; find gpurun_out/${tag}_pmc -type d -empty -delete
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"
+python bench.py --full > $OUT/${tag}_bench.json 2> $OUT/${tag}_bench.err && echo bench ok
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${tag}_prof -- python3 bench.py --full --no-cpu-baseline --no-stage0 --no-variants --no-gemm-ab > $OUT/${tag}_bench_under_rocprof.json 2> $OUT/${tag}_prof.err && echo prof ok
+f=$(find $OUT/${tag}_prof -name "*kernel_stats.csv" | head -1); cp "$f" $OUT/${tag}_bench_kernel_stats.csv; rm -rf $OUT/${tag}_prof
+bash scripts/pmc_passes.sh $OUT/${tag}_pmc_lin scripts/pmc_linear.py > $OUT/${tag}_pmc_linear_summary.json 2> $OUT/${tag}_pmc_lin.err && echo pmc linear ok
+find $OUT/${tag}_pmc_lin -name "*.csv" -delete; find $OUT/${tag}_pmc_lin -type d -empty -delete
+bash scripts/pmc_passes.sh $OUT/${tag}_pmc scripts/pmc_edit_steps.py 4 > $OUT/${tag}_pmc_edit_summary.json 2> $OUT/${tag}_pmc.err && echo pmc edit ok
+find $OUT/${tag}_pmc -name "*.csv" -delete; find $OUT/${tag}_pmc -type d -empty -delete
