@@ -435,16 +435,31 @@ class TokenTrie:
     n_tokens_dense: int        # B * S the dense forward would process
     tail: Optional[torch.Tensor] = None   # the caller's own int64 array uploaded with the trie (build_trie(tail=...))
     max_token: int = -1        # largest token id (host copy; -1: not recorded) — range check of the fused embedding kernel
+    position: Optional[torch.Tensor] = None   # (U,) int32 own position of every node: ``depth`` itself except on the query-only
+                                              # leaves of a multi-token trie (build_trie(eos=...)), where it is EOS + j
+    max_position: int = -1     # largest position (host copy; -1: not recorded)
+
+    def __post_init__(self):
+        if self.position is None:
+            self.position = self.depth
+        if self.max_position < 0:
+            self.max_position = int(self.anc.shape[1]) - 1
 
 
 ROW_BUCKET = 256   # node / query-row counts are padded to a multiple of this: a few GEMM shapes per encoder, not one per batch
 
 
-def build_trie(input_ids, lookup: Sequence[int], device, bucket: int = ROW_BUCKET, tail: Optional[np.ndarray] = None) -> TokenTrie:
+def build_trie(input_ids, lookup: Sequence[int], device, bucket: int = ROW_BUCKET, tail: Optional[np.ndarray] = None,
+               eos: Optional[np.ndarray] = None, pad_token: int = 0) -> TokenTrie:
     """Trie of the prompts' prefixes up to each lookup token.  ``input_ids``: (B, S) array (or equal-length rows).
     Nodes are numbered by depth, then by (parent, token).  Built by ``libemcid_host.so`` (``emcid_trie_build``: one packed image
     in pinned memory, ONE asynchronous upload) when that library is there, else level by level with numpy
-    (``build_trie_numpy``: six pageable uploads) — same arrays either way (tests/test_host_cpu.py)."""
+    (``build_trie_numpy``: six pageable uploads) — same arrays either way (tests/test_host_cpu.py).
+    ``eos`` (B,) given: the num_edit_tokens = k > 1 trie (``emcid_trie_build_leaves``): ``lookup`` is (B, k), every prompt's
+    chain runs through its EOS, and lookups behind the EOS are query-only leaves (token ``pad_token``, the EOS node's chain and
+    depth, own position EOS + j; include/emcid_host.h).  ``lookup_node`` / ``lookup_in_query`` then have B k entries, row-major."""
+    if eos is not None:
+        return _build_trie_leaves(input_ids, lookup, device, bucket, tail, eos, pad_token)
     tok = np.asarray(input_ids, dtype=np.int64)
     if tok.ndim != 2:
         raise UnsupportedEncoder("prompt rows of unequal length")
@@ -487,8 +502,60 @@ def build_trie(input_ids, lookup: Sequence[int], device, bucket: int = ROW_BUCKE
     return t
 
 
-def build_trie_numpy(tok: np.ndarray, lk: np.ndarray, device, bucket: int = ROW_BUCKET) -> TokenTrie:
+def _build_trie_leaves(input_ids, lookup, device, bucket: int, tail: Optional[np.ndarray], eos, pad_token: int) -> TokenTrie:
+    tok = np.asarray(input_ids, dtype=np.int64)
+    if tok.ndim != 2:
+        raise UnsupportedEncoder("prompt rows of unequal length")
+    lk = np.asarray(lookup, dtype=np.int64)
+    eos = np.asarray(eos, dtype=np.int64).reshape(-1)
+    B = tok.shape[0]
+    if lk.ndim != 2 or lk.shape[0] != B or eos.shape[0] != B or B == 0:
+        raise ValueError("a multi-token trie takes (B, k) lookups and (B,) EOS positions")
+    dmax = int(eos.max()) + 1
+    if dmax > 128:
+        raise UnsupportedEncoder("prompt longer than 128 tokens")
+    if int(eos.min()) < 0 or dmax > tok.shape[1] or int(lk.min()) < 0 or int(pad_token) < 0:
+        raise ValueError("EOS or lookup position outside the prompt rows")
+    read = tok[:, :dmax][np.arange(dmax)[None, :] <= eos[:, None]]          # the tokens of the chains
+    max_token = max(int(read.max()), int(pad_token)) if (lk > eos[:, None]).any() else int(read.max())
+    max_position = int(max(int(lk.max()), dmax - 1))
+    from . import host_text
+    if host_text.available() and int(read.min()) >= 0:
+        dev = torch.device(device)
+        extra = np.ascontiguousarray(tail, dtype=np.int64) if tail is not None else None
+        sizes = {}
+
+        def alloc(nbytes):
+            sizes["trie"] = (nbytes + 7) // 8 * 8
+            buf = torch.empty(sizes["trie"] + (extra.nbytes if extra is not None else 0), dtype=torch.uint8,
+                              pin_memory=(dev.type == "cuda"))
+            return buf, buf.data_ptr()
+
+        host, z = host_text.build_trie_packed(tok, lk, bucket, alloc, eos=eos, pad_token=int(pad_token))
+        if extra is not None:
+            host[sizes["trie"]:].view(torch.int64).copy_(torch.from_numpy(extra))
+        img = host.to(dev, non_blocking=True)
+        U, n, R, D = z["U"], z["n"], z["R_pad"], z["dmax"]
+        o32 = 8 * (U + 2 * n)
+        op = o32 + 4 * (U + R + U * D)
+        return TokenTrie(img[:8 * U].view(torch.int64), img[o32:o32 + 4 * U].view(torch.int32),
+                         img[o32 + 4 * (U + R):op].view(torch.int32).view(U, D),
+                         img[8 * U:8 * (U + n)].view(torch.int64), img[o32 + 4 * U:o32 + 4 * (U + R)].view(torch.int32),
+                         img[8 * (U + n):o32].view(torch.int64), z["n_real"], B * tok.shape[1],
+                         img[sizes["trie"]:].view(torch.int64) if extra is not None else None, max_token,
+                         img[op:op + 4 * U].view(torch.int32), max_position)
+    t = build_trie_numpy(tok, lk, device, bucket, eos=eos, pad_token=pad_token)
+    t.max_token, t.max_position = max_token, max_position
+    if tail is not None:
+        t.tail = torch.from_numpy(np.ascontiguousarray(tail, dtype=np.int64)).to(device)
+    return t
+
+
+def build_trie_numpy(tok: np.ndarray, lk: np.ndarray, device, bucket: int = ROW_BUCKET, eos: Optional[np.ndarray] = None,
+                     pad_token: int = 0) -> TokenTrie:
     """``build_trie`` with numpy: one ``np.unique`` over (parent, token) keys per position."""
+    if eos is not None:
+        return _build_trie_leaves_numpy(tok, lk, device, bucket, eos, pad_token)
     B = tok.shape[0]
     dmax = int(lk.max()) + 1
     vocab = int(tok[:, :dmax].max()) + 1
@@ -526,6 +593,68 @@ def build_trie_numpy(tok: np.ndarray, lk: np.ndarray, device, bucket: int = ROW_
                      torch.from_numpy(anc).to(device), torch.from_numpy(ln).to(device),
                      torch.from_numpy(q_rows.astype(np.int32)).to(device),
                      torch.from_numpy(inverse.astype(np.int64)).to(device), n_real, B * tok.shape[1])
+
+
+def _build_trie_leaves_numpy(tok: np.ndarray, lk: np.ndarray, device, bucket: int, eos: np.ndarray, pad_token: int) -> TokenTrie:
+    """The numpy twin of ``emcid_trie_build_leaves`` (same numbering: the chains level by level, then the leaves by (EOS node,
+    j), then the padding nodes)."""
+    tok = np.asarray(tok, dtype=np.int64)
+    lk = np.asarray(lk, dtype=np.int64)
+    eos = np.asarray(eos, dtype=np.int64).reshape(-1)
+    B, k = lk.shape
+    dmax = int(eos.max()) + 1
+    vocab = int(tok[:, :dmax][np.arange(dmax)[None, :] <= eos[:, None]].max()) + 1
+    node_of = np.full(B, -1, dtype=np.int64)
+    node_at = np.full((B, dmax), -1, dtype=np.int64)      # node of every prompt at every level of its chain
+    tokens, parents, levels = [], [], []
+    total = 0
+    for p in range(dmax):
+        alive = np.nonzero(eos >= p)[0]
+        key = (node_of[alive] + 1) * vocab + tok[alive, p]
+        uniq, inverse = np.unique(key, return_inverse=True)
+        node_of[alive] = total + inverse
+        node_at[alive, p] = node_of[alive]
+        tokens.append(uniq % vocab)
+        parents.append(uniq // vocab - 1)
+        levels.append(np.arange(total, total + uniq.size))
+        total += uniq.size
+    n_chain = total
+    behind = lk > eos[:, None]
+    j = np.where(behind, lk - eos[:, None], 0)
+    lf_key = node_of[:, None] * (int(j.max()) + 1) + j          # (EOS node, distance), ordered as the pair
+    lf_uniq, lf_inv = np.unique(lf_key[behind], return_inverse=True)
+    n_leaf = lf_uniq.size
+    lf_eos = lf_uniq // (int(j.max()) + 1)
+    lf_j = lf_uniq % (int(j.max()) + 1)
+    n_real = n_chain + n_leaf
+    pad = (-n_real) % bucket if bucket > 1 else 0
+    U = n_real + pad
+    token = np.concatenate(tokens + [np.full(n_leaf, pad_token, dtype=np.int64), np.full(pad, tokens[0][0], dtype=np.int64)])
+    parent = np.concatenate(parents)
+    depth = np.zeros(U, dtype=np.int32)
+    anc = np.zeros((U, dmax), dtype=np.int32)
+    for p, ids in enumerate(levels):
+        depth[ids] = p
+        if p:
+            anc[ids, :p] = anc[parent[ids], :p]
+        anc[ids, p] = ids
+    leaf_ids = np.arange(n_chain, n_real)
+    depth[leaf_ids] = depth[lf_eos]
+    anc[leaf_ids] = anc[lf_eos]
+    position = depth.copy()
+    position[leaf_ids] = depth[lf_eos] + lf_j
+    anc[n_real:, 0] = np.arange(n_real, U)
+    ln = np.where(behind, 0, node_at[np.arange(B)[:, None], np.minimum(lk, dmax - 1)])
+    ln[behind] = n_chain + lf_inv
+    ln = ln.reshape(-1)
+    q_rows, inverse = np.unique(ln, return_inverse=True)
+    if bucket > 1 and len(q_rows) % bucket:
+        q_rows = np.concatenate([q_rows, np.full((-len(q_rows)) % bucket, q_rows[0], dtype=q_rows.dtype)])
+    return TokenTrie(torch.from_numpy(token).to(device), torch.from_numpy(depth).to(device),
+                     torch.from_numpy(anc).to(device), torch.from_numpy(ln).to(device),
+                     torch.from_numpy(q_rows.astype(np.int32)).to(device),
+                     torch.from_numpy(inverse.reshape(-1).astype(np.int64)).to(device), n_real, B * tok.shape[1],
+                     position=torch.from_numpy(position).to(device), max_position=int(position.max()))
 
 
 class tuned_gemms:
@@ -616,7 +745,7 @@ def _check_fp32(graph: ClipTextGraph):
 
 
 def embed(graph: ClipTextGraph, trie: TokenTrie) -> torch.Tensor:
-    return graph.token_embedding(trie.token) + graph.position_embedding(trie.depth.long())
+    return graph.token_embedding(trie.token) + graph.position_embedding(trie.position.long())
 
 
 def _fusable(ln) -> bool:
@@ -716,18 +845,22 @@ def run_prefix(graph: ClipTextGraph, trie: TokenTrie, stop: int):
 
 def _run_prefix(graph: ClipTextGraph, trie: TokenTrie, stop: int):
     _check_fp32(graph)
+    if trie.position is not trie.depth and trie.max_position >= graph.position_embedding.num_embeddings:
+        # (a leaf behind the EOS past the position table: refused here, on the host, like HF's CLIP embeddings)
+        raise ValueError(f"Sequence length must be less than max_position_embeddings (position {trie.max_position} of "
+                         f"{graph.position_embedding.num_embeddings})")
     with tuned_gemms():
         ln0 = graph.layers[0].ln1 if stop > 0 and graph.layers else None
         te, pe = graph.token_embedding, graph.position_embedding
         if ln0 is not None and _fusable(ln0) and te.weight.is_cuda and te.weight.dtype == torch.float32 \
                 and te.weight.stride(1) == 1 and pe.weight.stride(1) == 1 and te.padding_idx is None and te.max_norm is None \
-                and pe.max_norm is None and trie.depth.dtype == torch.int32 and trie.token.dtype == torch.int64 \
-                and 0 <= trie.max_token < te.num_embeddings and trie.anc.shape[1] <= pe.num_embeddings:
+                and pe.max_norm is None and trie.position.dtype == torch.int32 and trie.token.dtype == torch.int64 \
+                and 0 <= trie.max_token < te.num_embeddings and trie.max_position < pe.num_embeddings:
             # embeddings + the first layer's LN1 in one launch; token and position ranges are checked on the host copies
             # (anything out of range takes the torch path, which raises like the reference's forward)
             sp0 = graph.layers[0].split_of("qkv") if graph.layers[0].qkv_w is not None else None
             if sp0 is not None and _sp_ln_ok(ln0):
-                hs, x_ln1 = hip.embed_layernorm_sp(te.weight, pe.weight, trie.token, trie.depth, ln0)
+                hs, x_ln1 = hip.embed_layernorm_sp(te.weight, pe.weight, trie.token, trie.position, ln0)
                 nat = native_of(graph, trie, 0, stop)
                 if nat is not None:
                     # every layer of the prefix in ONE C call (csrc/clip_layers.hip), in place on hs / the LN1 planes
@@ -739,7 +872,7 @@ def _run_prefix(graph: ClipTextGraph, trie: TokenTrie, stop: int):
                     LAST_PATHS["native_layers"] += stop
                     return hs, (x_ln1 if nxt is not None else None)
             else:
-                hs, x_ln1 = hip.embed_layernorm(te.weight, pe.weight, trie.token, trie.depth, ln0)
+                hs, x_ln1 = hip.embed_layernorm(te.weight, pe.weight, trie.token, trie.position, ln0)
         else:
             hs, x_ln1 = embed(graph, trie), None
         for i in range(stop):

@@ -164,6 +164,9 @@ class PromptChunk:
     n_requests: int
     verify: Optional[Callable[[], bool]] = None      # deferred tokenizer cross-check (templated_prompt_chunk), None = already done
     offsets: Optional[np.ndarray] = None             # (n_requests + 1,) int64 prompt offsets of the requests, when already known
+    eos: Optional[np.ndarray] = None                 # num_edit_tokens = k > 1: (B_c,) int64 EOS position per prompt; the rows are
+                                                     # then kept through their EOS and ``lookup`` is (B_c, k): [last subject
+                                                     # token, EOS, EOS + 1, ..., EOS + k - 2] (reference compute_z.py:2329-2360)
 
     def request_offsets(self) -> np.ndarray:
         if self.offsets is None:
@@ -174,7 +177,16 @@ class PromptChunk:
 _GET_SOURCE, _GET_PROMPTS = operator.itemgetter("source"), operator.itemgetter("prompts")
 
 
-def templated_prompt_chunk(tokenizer, requests: Sequence[Dict], first: Dict, defer_probe: bool = False) -> Optional[PromptChunk]:
+def multi_token_lookup(last_subject: np.ndarray, eos: np.ndarray, k: int) -> np.ndarray:
+    """(B, k) rows of a num_edit_tokens = k > 1 edit: [last subject token, EOS, EOS + 1, ..., EOS + k - 2] per prompt (the order
+    of build_prompt_batch_multi, reference compute_z.py:2329-2382)."""
+    last_subject = np.asarray(last_subject, dtype=np.int64).reshape(-1, 1)
+    eos = np.asarray(eos, dtype=np.int64).reshape(-1, 1)
+    return np.ascontiguousarray(np.concatenate([last_subject, eos + np.arange(k - 1, dtype=np.int64)[None, :]], axis=1))
+
+
+def templated_prompt_chunk(tokenizer, requests: Sequence[Dict], first: Dict, defer_probe: bool = False,
+                           num_edit_tokens: int = 1) -> Optional[PromptChunk]:
     """The (few templates) x (many names) shape of a mass edit WITHOUT building, joining and re-splitting the prompt strings:
     ``p.format(source)`` (reference compute_z.py:2278-2283) for templates with exactly one ``{}`` and no other brace is
     ``prefix + source + suffix``, so ``libemcid_host`` encodes every distinct prefix, suffix and source once
@@ -184,7 +196,8 @@ def templated_prompt_chunk(tokenizer, requests: Sequence[Dict], first: Dict, def
     tokenizer without a native twin, a non-string source) and the caller takes the generic path.  ``defer_probe``: the
     per-call comparison of the longest row against the public tokenizer call (a never-seen prompt: ~0.1 ms of the HF
     tokenizer) is handed back as ``chunk.verify`` instead of being run here — the engine calls it after it has launched the
-    leading layers and redoes the preparation on the generic path if it ever says no."""
+    leading layers and redoes the preparation on the generic path if it ever says no.  ``num_edit_tokens`` = k > 1: the rows
+    are kept through their EOS and the chunk carries the EOS positions and (B, k) lookups (``PromptChunk.eos``)."""
     if "source_prompts" in first or "prompts" not in first or len(requests) < 3 or getattr(tokenizer, "_tokenizer", None) is None:
         return None
     twin = host_text.NativeClipBpe.for_tokenizer(tokenizer)
@@ -288,13 +301,19 @@ def templated_prompt_chunk(tokenizer, requests: Sequence[Dict], first: Dict, def
     else:
         lk = walk()
         verify = probe_agrees if defer_probe else None
+    if num_edit_tokens > 1:
+        eos = lengths.astype(np.int64) - 1
+        return PromptChunk(np.ascontiguousarray(ids[:, :int(eos.max()) + 1]), multi_token_lookup(lk, eos, num_edit_tokens), counts,
+                           n, verify=verify, offsets=offsets, eos=eos)
     return PromptChunk(np.ascontiguousarray(ids[:, :int(lk.max()) + 1]), lk, counts, n, verify=verify, offsets=offsets)
 
 
-def iter_prompt_chunks(tokenizer, requests: Sequence[Dict], n_chunks: int, defer_probe: bool = False):
+def iter_prompt_chunks(tokenizer, requests: Sequence[Dict], n_chunks: int, defer_probe: bool = False, num_edit_tokens: int = 1):
     """The request list in ``n_chunks`` contiguous slices, each tokenized, searched and truncated on its own, lazily: the
     caller builds a slice's prefix trie and launches its share of the encoder forward before asking for the next slice,
-    so the GPU works on slice i while the host tokenizes slice i+1 (no helper thread: the launches are asynchronous)."""
+    so the GPU works on slice i while the host tokenizes slice i+1 (no helper thread: the launches are asynchronous).
+    ``num_edit_tokens`` = k > 1: each row is kept through its EOS and the chunk carries (B, k) lookups and the EOS positions."""
+    k = int(num_edit_tokens)
     n = len(requests)
     n_chunks = max(1, min(n_chunks, n))
     first = requests[0]
@@ -302,12 +321,13 @@ def iter_prompt_chunks(tokenizer, requests: Sequence[Dict], n_chunks: int, defer
     for i in range(n_chunks):
         lo, hi = (n * i) // n_chunks, (n * (i + 1)) // n_chunks
         if os.environ.get("EMCID_TEMPLATED", "1") != "0":
-            fast = templated_prompt_chunk(tokenizer, requests[lo:hi], first, defer_probe)
+            fast = templated_prompt_chunk(tokenizer, requests[lo:hi], first, defer_probe, k)
             if fast is not None:
                 yield fast
                 continue
         prompts, subjects, counts = expand_request_prompts(requests[lo:hi], first)
-        ids = tokenize_lists(tokenizer, prompts)["input_ids"]
+        enc = tokenize_lists(tokenizer, prompts)
+        ids = enc["input_ids"]
         lookup = [r[-1] - 1 for r in finder.batch(ids, subjects)]
         lk = np.asarray(lookup, dtype=np.int64)
         bad = np.nonzero((lk < 0) | (lk >= ids.shape[1]))[0]
@@ -316,6 +336,11 @@ def iter_prompt_chunks(tokenizer, requests: Sequence[Dict], n_chunks: int, defer
             raise ValueError(f"lookup index {lookup[j]} outside the padded prompt (S={ids.shape[1]}) for prompt {prompts[j]!r}")
         if sum(counts) != len(prompts):
             raise ValueError(f"request prompt counts ({sum(counts)}) do not cover the {len(prompts)} prompts")
+        if k > 1:
+            eos = np.asarray(enc["attention_mask"], dtype=np.int64).sum(axis=1) - 1
+            yield PromptChunk(np.ascontiguousarray(ids[:, :int(eos.max()) + 1]), multi_token_lookup(lk, eos, k), counts, hi - lo,
+                              eos=eos)
+            continue
         yield PromptChunk(np.ascontiguousarray(ids[:, :int(lk.max()) + 1]), lookup, counts, hi - lo)
 
 

@@ -35,7 +35,7 @@ const char* header_value(const std::string& h, const char* key) {
 }
 
 // 0 = row written; 1 = no such file; 2 = not servable here (caller: numpy).  `buf` is the thread's scratch.
-int read_one(const char* path, const char* member, int64_t width, float* out, std::vector<unsigned char>& buf) {
+int read_one(const char* path, const char* member, int64_t rows, int64_t width, float* out, std::vector<unsigned char>& buf) {
     // O_NOATIME: the first read of a freshly written file moves its access time (relatime), i.e. dirties the inode and takes a
     // journal handle — and that waits while the file system commits a large transaction (a burst of file creations a few seconds
     // earlier: bench.py's 26 000 cache files; profiles/r05_outlier.txt: one call in twenty 150-210 ms, all of it in these reads).
@@ -108,15 +108,15 @@ int read_one(const char* path, const char* member, int64_t width, float* out, st
     if (*p != ')') return 2;
     // a vector of `width`, or the (1, width) layout of the reference's use_new_compute_z files (:951-968); a Fortran-ordered
     // vector is the same bytes
-    const bool vec = dims == 1 && count == width;
-    const bool row = dims == 2 && lead == 1 && count == width;
+    // (k rows of a use_new_compute_z file with k > 1: C order only)
+    const bool vec = rows == 1 && dims == 1 && count == width;
+    const bool row = dims == 2 && lead == rows && count == rows * width && (rows == 1 || strncmp(order, "False", 5) == 0);
     if (!vec && !row) return 2;
-    (void)order;      // a vector (or one row) has the same bytes in either order
     if (o + (size_t)count * item > n) return 2;
     if (item == 4) {
-        memcpy(out, b + o, (size_t)width * 4);
+        memcpy(out, b + o, (size_t)count * 4);
     } else {
-        for (int64_t i = 0; i < width; ++i) {
+        for (int64_t i = 0; i < count; ++i) {
             double v;
             memcpy(&v, b + o + (size_t)i * 8, 8);
             out[i] = (float)v;      // numpy's astype(float32): round to nearest even, like this conversion
@@ -129,7 +129,13 @@ int read_one(const char* path, const char* member, int64_t width, float* out, st
 
 extern "C" int64_t emcid_read_npz_rows_f32(const char* paths, const int64_t* off, int64_t n, const char* member, int64_t width,
                                            float* out, int64_t ld, uint8_t* status, int32_t n_threads) {
-    if (!paths || !off || n < 0 || !member || width <= 0 || !out || ld < width || !status) return -1;
+    return emcid_read_npz_rows_k_f32(paths, off, n, member, 1, width, out, ld, status, n_threads);
+}
+
+extern "C" int64_t emcid_read_npz_rows_k_f32(const char* paths, const int64_t* off, int64_t n, const char* member, int64_t rows,
+                                             int64_t width, float* out, int64_t ld, uint8_t* status, int32_t n_threads) {
+    if (!paths || !off || n < 0 || !member || rows <= 0 || width <= 0 || rows * width > (1 << 26) || !out || ld < rows * width || !status)
+        return -1;
     if (n == 0) return 0;
     int nt = n_threads < 1 ? 1 : n_threads > 64 ? 64 : n_threads;
     if ((int64_t)nt > (n + 63) / 64) nt = (int)((n + 63) / 64);      // at least 64 files per thread
@@ -142,7 +148,7 @@ extern "C" int64_t emcid_read_npz_rows_f32(const char* paths, const int64_t* off
             std::string path;
             for (; i < hi; ++i) {
                 path.assign(paths + off[i], (size_t)(off[i + 1] - off[i]));
-                status[i] = (uint8_t)read_one(path.c_str(), member, width, out + i * ld, buf);
+                status[i] = (uint8_t)read_one(path.c_str(), member, rows, width, out + i * ld, buf);
             }
         } catch (...) {
             for (; i < hi; ++i) status[i] = 2;

@@ -129,7 +129,7 @@ struct emcid_bpe {
 
 extern "C" {
 
-int emcid_host_abi_version(void) { return 5; }
+int emcid_host_abi_version(void) { return 6; }
 
 const char* emcid_host_last_error(void) { return g_error.c_str(); }
 
@@ -554,37 +554,24 @@ struct emcid_trie {
     int32_t dmax = 0;
     std::vector<int64_t> token, lookup_node, inverse;
     std::vector<int32_t> depth, parent, q_rows;
+    std::vector<int32_t> position;         // own position of every node (emcid_trie_build_leaves only; empty: position = depth)
     std::vector<int64_t> level_begin;      // first node of each level (dmax + 1 entries)
 };
 
-emcid_trie* emcid_trie_build(const int64_t* ids, int64_t n, int64_t S, const int64_t* lookup, int64_t bucket) {
-    if (!ids || !lookup || n <= 0 || S <= 0 || bucket < 1) {
-        g_error = "emcid_trie_build: bad argument";
-        return nullptr;
-    }
-    int64_t lmax = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        if (lookup[i] < 0 || lookup[i] >= S) {
-            g_error = "emcid_trie_build: lookup index outside the row";
-            return nullptr;
-        }
-        if (lookup[i] > lmax) lmax = lookup[i];
-    }
-    auto* t = new emcid_trie();
-    t->n = n;
-    t->dmax = (int32_t)(lmax + 1);
-    t->lookup_node.assign((size_t)n, -1);
+// The chains: levels 0 .. end[i] of every prompt, numbered level by level, inside a level by (parent, token).  node_of[i]: node of
+// prompt i at its last level.  false (g_error set) on a negative token id.
+static bool build_chains(emcid_trie* t, const int64_t* ids, int64_t n, int64_t S, const int64_t* end, std::vector<int64_t>& node_of) {
+    node_of.assign((size_t)n, -1);
     t->level_begin.push_back(0);
     // keys (parent + 1) * vocab + token, sorted per level by an LSD radix sort (11-bit digits): a comparison sort of the ~n
     // entries of every level was most of the build's time
     int64_t vocab = 1;
     for (int64_t i = 0; i < n; ++i)
-        for (int64_t p = 0; p <= lookup[i]; ++p) {
+        for (int64_t p = 0; p <= end[i]; ++p) {
             const int64_t tk = ids[i * S + p];
             if (tk < 0) {
-                delete t;
                 g_error = "emcid_trie_build: negative token id";
-                return nullptr;
+                return false;
             }
             if (tk >= vocab) vocab = tk + 1;
         }
@@ -592,13 +579,12 @@ emcid_trie* emcid_trie_build(const int64_t* ids, int64_t n, int64_t S, const int
     std::vector<Entry> cur, tmp;
     cur.reserve((size_t)n);
     tmp.reserve((size_t)n);
-    std::vector<int64_t>& node_of = t->lookup_node;     // node of each prompt at the level just built (its last alive level stays)
     int64_t total = 0;
     for (int32_t p = 0; p < t->dmax; ++p) {
         cur.clear();
         uint64_t kmax = 0;
         for (int64_t i = 0; i < n; ++i)
-            if (lookup[i] >= p) {
+            if (end[i] >= p) {
                 const uint64_t key = (uint64_t)(node_of[(size_t)i] + 1) * (uint64_t)vocab + (uint64_t)ids[i * S + p];
                 if (key > kmax) kmax = key;
                 cur.push_back({key, i});
@@ -625,14 +611,21 @@ emcid_trie* emcid_trie_build(const int64_t* ids, int64_t n, int64_t S, const int
         t->level_begin.push_back(total);
     }
     t->n_real = total;
+    return true;
+}
+
+// Padding nodes and the query rows of t->lookup_node (n lookups).
+static void finish_trie(emcid_trie* t, int64_t n, int64_t bucket) {
+    const int64_t total = t->n_real;
     const int64_t pad = bucket > 1 ? (bucket - total % bucket) % bucket : 0;
     t->U = total + pad;
     for (int64_t k = 0; k < pad; ++k) {       // padding nodes: copies of the first root token at depth 0, attending to themselves
         t->token.push_back(t->token[0]);
         t->depth.push_back(0);
         t->parent.push_back(-1);
+        if (!t->position.empty()) t->position.push_back(0);
     }
-    // distinct lookup nodes, sorted, and each prompt's index among them: mark the nodes, then one scan in node order
+    // distinct lookup nodes, sorted, and each lookup's index among them: mark the nodes, then one scan in node order
     std::vector<int32_t> rank((size_t)total, -1);
     for (int64_t i = 0; i < n; ++i) rank[(size_t)t->lookup_node[(size_t)i]] = 0;
     t->q_rows.clear();
@@ -649,6 +642,95 @@ emcid_trie* emcid_trie_build(const int64_t* ids, int64_t n, int64_t S, const int
         t->q_rows.resize((size_t)(t->R + (bucket - t->R % bucket)), q0);
     }
     t->R_pad = (int64_t)t->q_rows.size();
+}
+
+emcid_trie* emcid_trie_build(const int64_t* ids, int64_t n, int64_t S, const int64_t* lookup, int64_t bucket) {
+    if (!ids || !lookup || n <= 0 || S <= 0 || bucket < 1) {
+        g_error = "emcid_trie_build: bad argument";
+        return nullptr;
+    }
+    int64_t lmax = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (lookup[i] < 0 || lookup[i] >= S) {
+            g_error = "emcid_trie_build: lookup index outside the row";
+            return nullptr;
+        }
+        if (lookup[i] > lmax) lmax = lookup[i];
+    }
+    auto* t = new emcid_trie();
+    t->n = n;
+    t->dmax = (int32_t)(lmax + 1);
+    if (!build_chains(t, ids, n, S, lookup, t->lookup_node)) {      // (node of each prompt at its last level = its lookup node)
+        delete t;
+        return nullptr;
+    }
+    finish_trie(t, n, bucket);
+    return t;
+}
+
+emcid_trie* emcid_trie_build_leaves(const int64_t* ids, int64_t n, int64_t S, const int64_t* lookup, int64_t k, const int64_t* eos,
+                                    int64_t pad_token, int64_t bucket) {
+    if (!ids || !lookup || !eos || n <= 0 || S <= 0 || k < 1 || bucket < 1 || pad_token < 0) {
+        g_error = "emcid_trie_build_leaves: bad argument";
+        return nullptr;
+    }
+    int64_t emax = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (eos[i] < 0 || eos[i] >= S) {
+            g_error = "emcid_trie_build_leaves: EOS index outside the row";
+            return nullptr;
+        }
+        for (int64_t j = 0; j < k; ++j)
+            if (lookup[i * k + j] < 0 || lookup[i * k + j] - eos[i] >= (1 << 20)) {
+                g_error = "emcid_trie_build_leaves: lookup position out of range";
+                return nullptr;
+            }
+        if (eos[i] > emax) emax = eos[i];
+    }
+    auto* t = new emcid_trie();
+    t->n = n * k;
+    t->dmax = (int32_t)(emax + 1);
+    std::vector<int64_t> eos_node;
+    if (!build_chains(t, ids, n, S, eos, eos_node)) {
+        delete t;
+        return nullptr;
+    }
+    const int64_t n_chain = t->n_real;
+    t->position.assign(t->depth.begin(), t->depth.end());
+    // lookups at or before the EOS: the prompt's chain node at that level (up the parent links from the EOS node); behind it:
+    // query-only leaves keyed by (EOS node, distance), numbered after every chain node in that order
+    t->lookup_node.assign((size_t)(n * k), -1);
+    std::vector<std::pair<int64_t, int64_t>> leaves;
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t j = 0; j < k; ++j) {
+            const int64_t pos = lookup[i * k + j];
+            if (pos > eos[i]) {
+                leaves.push_back({eos_node[(size_t)i], pos - eos[i]});
+                continue;
+            }
+            int64_t u = eos_node[(size_t)i];
+            for (int64_t up = eos[i]; up > pos; --up) u = t->parent[(size_t)u];
+            t->lookup_node[(size_t)(i * k + j)] = u;
+        }
+    std::sort(leaves.begin(), leaves.end());
+    leaves.erase(std::unique(leaves.begin(), leaves.end()), leaves.end());
+    for (const auto& lf : leaves) {
+        const int32_t d = t->depth[(size_t)lf.first];
+        t->token.push_back(pad_token);
+        t->parent.push_back((int32_t)lf.first);
+        t->depth.push_back(d);                       // the attention chain is the EOS node's: keys 0 .. EOS
+        t->position.push_back((int32_t)(d + lf.second));
+    }
+    t->n_real = n_chain + (int64_t)leaves.size();
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t j = 0; j < k; ++j) {
+            const int64_t pos = lookup[i * k + j];
+            if (pos > eos[i]) {
+                const auto it = std::lower_bound(leaves.begin(), leaves.end(), std::make_pair(eos_node[(size_t)i], pos - eos[i]));
+                t->lookup_node[(size_t)(i * k + j)] = n_chain + (int64_t)(it - leaves.begin());
+            }
+        }
+    finish_trie(t, n * k, bucket);
     return t;
 }
 
@@ -662,7 +744,7 @@ void emcid_trie_sizes(const emcid_trie* t, int64_t* U, int64_t* n_real, int64_t*
 
 int64_t emcid_trie_packed_bytes(const emcid_trie* t) {
     if (!t) return -1;
-    const int64_t i32s = t->U + t->R_pad + t->U * t->dmax;
+    const int64_t i32s = t->U + t->R_pad + t->U * t->dmax + (t->position.empty() ? 0 : t->U);
     return 8 * (t->U + 2 * t->n) + 4 * (i32s + (i32s & 1));
 }
 
@@ -681,11 +763,17 @@ int emcid_trie_export(const emcid_trie* t, void* out, int64_t out_bytes) {
     int32_t* anc = p32 + t->U + t->R_pad;
     const int32_t D = t->dmax;
     std::memset(anc, 0, (size_t)t->U * D * 4);
+    const bool leaves = !t->position.empty();
     for (int64_t u = 0; u < t->U; ++u) {            // parents precede their children: copy the parent's chain, append self
         const int32_t d = t->depth[(size_t)u], par = t->parent[(size_t)u];
+        if (leaves && t->position[(size_t)u] != d) {      // a query-only leaf: the chain of its EOS node, that node included
+            std::memcpy(anc + u * D, anc + (int64_t)par * D, (size_t)(d + 1) * 4);
+            continue;
+        }
         if (d > 0) std::memcpy(anc + u * D, anc + (int64_t)par * D, (size_t)d * 4);
         anc[u * D + d] = (int32_t)u;
     }
+    if (leaves) std::memcpy(anc + t->U * D, t->position.data(), (size_t)t->U * 4);
     return 0;
 }
 

@@ -77,6 +77,40 @@ class TrieChunk:
     n_requests: int
     n_prompts: int
     state: Optional[tuple] = None          # (layer index, residual stream, LN1 of it | None)
+    # the gather of the keys: one segment per CONCEPT.  k = 1: the trie's own lookup arrays and ``seg``.  k > 1: the B k lookups
+    # reordered into (request, num) pseudo-segments of the request's P prompts each, concept rq k + num (the reference's
+    # "rq num" order, emcid_main.py:993-1014), so that the one gather-mean kernel yields the N k rows in that order
+    lookup_node: Optional[torch.Tensor] = None     # (B k,) int64 node of every lookup, concept order (edited layers before the last)
+    lookup_query: Optional[torch.Tensor] = None    # (B k,) int64 its index among the trie's query rows (the last edited layer)
+    cseg: Optional[torch.Tensor] = None            # (n_requests k + 1,) int64 offsets of the concepts' segments
+
+    def __post_init__(self):
+        if self.lookup_node is None:
+            self.lookup_node, self.lookup_query, self.cseg = self.trie.lookup_node, self.trie.lookup_in_query, self.seg
+
+
+def concept_bounds(plan, r: Optional[int] = None):
+    """``EncoderEditPlan.concept_bounds`` for anything with ``shard``, ``n_total`` (and ``num_edit_tokens``, default 1)."""
+    k = int(getattr(plan, "num_edit_tokens", 1) or 1)
+    lo, hi = plan.shard.bounds(plan.n_total // k, r)
+    return lo * k, hi * k
+
+
+def concept_segments(counts, k: int):
+    """(perm (B k,), cseg (N k + 1,)) of the pseudo-segments: concept rq k + num gathers the lookups p k + num of the request's
+    prompts p, in prompt order (position k s_rq + num c_rq + (p - s_rq) of ``perm``; s: prompt offsets, c: prompt counts)."""
+    c = np.asarray(counts, dtype=np.int64)
+    s = np.concatenate([[0], np.cumsum(c)]).astype(np.int64)
+    B = int(s[-1])
+    req = np.repeat(np.arange(c.size), c)
+    w = np.arange(B, dtype=np.int64) - s[req]
+    num = np.arange(k, dtype=np.int64)
+    perm = np.empty(B * k, dtype=np.int64)
+    perm[(k * s[req] + w)[:, None] + num[None, :] * c[req][:, None]] = np.arange(B, dtype=np.int64)[:, None] * k + num[None, :]
+    cseg = np.empty(c.size * k + 1, dtype=np.int64)
+    cseg[:-1] = (k * s[:-1, None] + num[None, :] * c[:, None]).reshape(-1)
+    cseg[-1] = B * k
+    return perm, cseg
 
 
 @dataclass
@@ -109,6 +143,12 @@ class EncoderEditPlan:
 
     def weight_name(self, layer):
         return f"{self.rewrite_module_tmp.format(layer)}.weight"
+
+    def concept_bounds(self, r: Optional[int] = None):
+        """Rank ``r``'s (default: this rank's) rows [lo, hi) of the N k concepts: k times its request range — the request
+        split decides everything (a rank's concepts come from its own prompts), so this, not bounds(n_total), sizes every
+        K / Zc / v* row block and row-sharded solve."""
+        return concept_bounds(self, r)
 
     @property
     def trie(self):                        # the (first) trie of the prefix-deduplicated forward, None on the hooked-HF path
@@ -296,13 +336,11 @@ def prepare_encoder_edit(text_encoder, tokenizer, requests: Sequence[Dict], laye
     k = int(num_edit_tokens)
     if k < 1:
         raise ValueError(f"num_edit_tokens must be >= 1, got {k}")
-    if k > 1:
-        # k rows per request ([last subject token, EOS, k - 2 padding positions], reference compute_z.py:2329-2382 and
-        # emcid_main.py:993-1014): the rows behind the EOS need the padded prompts, so this runs on the hooked forward over the
-        # padded batch (no prefix trie, no token truncation) and on one rank; the closed form then sees N k concepts
-        if shard.collective:
-            raise NotImplementedError("num_edit_tokens > 1 is a single-rank path")
-        mode = "hf"
+    # k > 1: k rows per request ([last subject token, EOS, k - 2 padding positions], reference compute_z.py:2329-2382 and
+    # emcid_main.py:993-1014), N k concepts.  On the trie the rows behind the EOS are query-only leaves (clip_forward.build_trie);
+    # the one batch-wide effect of the padding, the padded length longest + k - 2 against the position table, is checked on
+    # every rank before anything is launched (_check_padded_length)
+    length_checked = k == 1
     if mode == "trie" and layer_module_tmp is not None and device.type == "cuda":
         try:
             with phase("graph"):
@@ -327,18 +365,38 @@ def prepare_encoder_edit(text_encoder, tokenizer, requests: Sequence[Dict], laye
         first_edit = plan.layers[0]
         chunks: List[TrieChunk] = []
         try:
-            it = iter_prompt_chunks(tokenizer, local, n_chunks, defer_probe=_defer_checks)
+            # (k > 1: every check of the tokenization up front — a restarted preparation on one rank would pair its collective
+            # with another rank's next one)
+            it = iter_prompt_chunks(tokenizer, local, n_chunks, defer_probe=_defer_checks and k == 1, num_edit_tokens=k)
             while True:
                 with phase("tokenize+lookup"):
                     pc = next(it, None)
                 if pc is None:
                     break
-                with phase("trie"):
-                    trie = clip_forward.build_trie(pc.ids, pc.lookup, device, tail=pc.request_offsets())
-                    seg = trie.tail
+                if k > 1:
+                    if not length_checked:
+                        _check_padded_length(shard, int(pc.eos.max()) + 1, k, graph.position_embedding.num_embeddings, device)
+                        length_checked = True
+                    with phase("trie"):
+                        pad = getattr(tokenizer, "pad_token_id", None)
+                        if pad is None and k > 2:
+                            raise ValueError("num_edit_tokens > 2 pads the prompts: the tokenizer has no pad token")
+                        perm, cseg = concept_segments(pc.counts, k)
+                        offs = pc.request_offsets()
+                        trie = clip_forward.build_trie(pc.ids, pc.lookup, device, tail=np.concatenate([offs, cseg, perm]),
+                                                       eos=pc.eos, pad_token=int(pad or 0))
+                        n1, n2 = offs.size, offs.size + cseg.size
+                        seg, cseg_d, perm_d = trie.tail[:n1], trie.tail[n1:n2], trie.tail[n2:]
+                        chunk = TrieChunk(trie, seg, pc.n_requests, len(pc.lookup), None, trie.lookup_node.index_select(0, perm_d),
+                                          trie.lookup_in_query.index_select(0, perm_d), cseg_d)
+                else:
+                    with phase("trie"):
+                        trie = clip_forward.build_trie(pc.ids, pc.lookup, device, tail=pc.request_offsets())
+                        chunk = TrieChunk(trie, trie.tail, pc.n_requests, len(pc.lookup))
                 with phase("prefix launches"), torch.no_grad():
                     hs, x_ln1 = clip_forward.run_prefix(graph, trie, first_edit)
-                chunks.append(TrieChunk(trie, seg, pc.n_requests, len(pc.lookup), (first_edit, hs, x_ln1)))
+                chunk.state = (first_edit, hs, x_ln1)
+                chunks.append(chunk)
                 if pc.verify is not None:
                     # the checks of the templated tokenization that need not hold the first launch back — the native tokenizer's
                     # cross-check against the public tokenizer call, the reference's subject walk against the lookup positions
@@ -359,7 +417,11 @@ def prepare_encoder_edit(text_encoder, tokenizer, requests: Sequence[Dict], laye
             plan.graph = plan.chunks = None
     if plan.chunks is None:
         with phase("tokenize+lookup"):
-            plan.ensure_batch()
+            batch = plan.ensure_batch()
+        if not length_checked:
+            # (the hooked forward pads this rank's prompts to ITS longest + k - 2; the reference pads every prompt to the global one)
+            n_pos = getattr(getattr(text_encoder, "config", None), "max_position_embeddings", None)
+            _check_padded_length(shard, int(batch.inputs["attention_mask"].sum(dim=1).max().item()), k, n_pos, device)
     # ``zs_t`` / ``covs`` may be callables: the caller's v* cache check and statistics lookups, run HERE — after the leading
     # layers have been launched, so that these host milliseconds too pass underneath the GPU (v* first, as the reference)
     if callable(zs_t) and not hasattr(zs_t, "result"):
@@ -373,6 +435,23 @@ def prepare_encoder_edit(text_encoder, tokenizer, requests: Sequence[Dict], laye
     if not hasattr(zs_t, "result"):
         plan.resolve_targets()
     return plan
+
+
+def _check_padded_length(shard: ConceptShard, longest: int, k: int, n_positions: Optional[int], device):
+    """The reference pads every prompt of a k > 1 edit to (longest + k - 2) tokens (compute_z.py:2329-2360) — the longest over
+    ALL requests — and HF's CLIP embeddings refuse a sequence longer than the position table.  Raised on every rank, the same
+    verdict everywhere (one MAX all-reduce of the local longest under a collective shard), before anything is launched."""
+    if shard.collective:
+        import torch.distributed as dist
+        dev = torch.device(device)
+        t = torch.tensor([int(longest)], dtype=torch.int64,
+                         device=dev if dev.type == "cuda" and not _staged(shard.group) else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=shard.group)
+        longest = int(t.item())
+    if n_positions is not None and longest + k - 2 > int(n_positions):
+        raise ValueError(f"Sequence length must be less than max_position_embeddings (got `sequence length`: {longest + k - 2} "
+                         f"and max_position_embeddings: {int(n_positions)}): num_edit_tokens = {k} pads the longest prompt "
+                         f"({longest} tokens) by {k - 2}")
 
 
 def _staged(group) -> bool:
@@ -446,7 +525,7 @@ def _all_gather_rows(local: torch.Tensor, plan: EncoderEditPlan) -> torch.Tensor
 
 
 def _all_gather_rows_timed(local, plan, sh, dist):
-    sizes = [b - a for a, b in (sh.bounds(plan.n_total, r) for r in range(sh.world))]
+    sizes = [b - a for a, b in (concept_bounds(plan, r) for r in range(sh.world))]
     nmax = max(sizes)
     padded = local
     if local.shape[0] < nmax:
@@ -610,7 +689,7 @@ def run_encoder_edit(plan: EncoderEditPlan, keep_factors: bool = False, trace: b
                 split = False
                 res = hip.edit_layer_dual_apply(
                     K, Zc, plan.zs_t, plan.cov_factors, i, plan.edit_weight, L - i, backups[layer], weights[layer].data,
-                    ws=plan.dual_ws, rows=plan.shard.bounds(plan.n_total) if split else None,
+                    ws=plan.dual_ws, rows=plan.concept_bounds() if split else None,
                     gather_yt=(lambda rows_: _all_gather_rows(rows_.contiguous(), plan)) if split else None,
                     on_factor_start=lazy_inverse if ahead else None, lam=solve_lam(plan))
                 edits.append(LayerEdit(layer, plan.weight_name(layer), res["dW"], None, None,
@@ -619,7 +698,7 @@ def run_encoder_edit(plan: EncoderEditPlan, keep_factors: bool = False, trace: b
             res = hip.edit_layer_dual(
                 K, Zc, plan.zs_t, plan.cov_factors, i, plan.edit_weight, L - i, W0=backups[layer], W=weights[layer].data,
                 want_factors=keep_factors, ws=plan.dual_ws,
-                rows=plan.shard.bounds(plan.n_total) if sharded else None,
+                rows=plan.concept_bounds() if sharded else None,
                 gather_pt=(lambda rows_: _all_gather_rows(rows_.contiguous(), plan)) if sharded else None, lam=solve_lam(plan))
             xt = res["adj_k"].t() if res["adj_k"] is not None else None
             edits.append(LayerEdit(layer, plan.weight_name(layer), res["dW"], xt, res["Rt"],
@@ -638,7 +717,7 @@ def run_encoder_edit(plan: EncoderEditPlan, keep_factors: bool = False, trace: b
             # every rank assembles and factors A from all N concepts; the triangular solves and the dW
             # contraction are split by concept rows and the partial U summed over xGMI (fp64, h*d*8 bytes)
             res = hip.edit_layer_shard(K, Zc, plan.zs_t, plan.covs[layer], plan.lam, plan.edit_weight, L - i,
-                                       plan.shard.bounds(plan.n_total), ws=plan.ws)
+                                       plan.concept_bounds(), ws=plan.ws)
             _all_reduce_sum(res["U"], plan.shard.group)
             dW = hip.apply_update_(res["U"], backups[layer], weights[layer].data)
             res = {"dW": dW, "Xt": None, "Rt": None}
@@ -654,13 +733,13 @@ def run_encoder_edit(plan: EncoderEditPlan, keep_factors: bool = False, trace: b
             raise RuntimeError("hparams.layers must be in forward order")
         first_edit = plan.layers[0]
 
-        def rows_at(x, idx, ch):   # (rows, c) activations -> per-request means at each prompt's lookup row
+        def rows_at(x, idx, ch):   # (rows, c) activations -> per-concept means at the lookup rows of its prompts
             if isinstance(x, hip.SplitRows):       # split-fp16 path: the keys come from the fp32 twin fc1's epilogue wrote
                 x = x.float()
-            return hip.gather_mean(x.unsqueeze(0).expand(idx.numel(), -1, -1), idx, ch.seg)
+            return hip.gather_mean(x.unsqueeze(0).expand(idx.numel(), -1, -1), idx, ch.cseg)
 
-        def keys(li, xs):          # this rank's (N_local, d) key rows, slices concatenated in request order
-            parts = [rows_at(x, ch.trie.lookup_in_query if li == last else ch.trie.lookup_node, ch) for x, ch in zip(xs, chunks)]
+        def keys(li, xs):          # this rank's (N_local k, d) key rows, slices concatenated in request order
+            parts = [rows_at(x, ch.lookup_query if li == last else ch.lookup_node, ch) for x, ch in zip(xs, chunks)]
             return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
 
         zc_from_keys = True      # Zc = fc2(mean keys): fc2 is affine (the other form, fc2 over every node + gather, left in round 5)
@@ -696,8 +775,8 @@ def run_encoder_edit(plan: EncoderEditPlan, keep_factors: bool = False, trace: b
                 w = weights[li]
                 try:
                     res = hip.clip_edit_layer_tail(
-                        nat.array, li, nat.h, nat.d, x, mids[0], ch.trie.lookup_in_query if li == last else ch.trie.lookup_node,
-                        ch.seg, plan.zs_t, plan.cov_factors, i, plan.edit_weight, L - i, backups[li], w.data, plan.dual_ws,
+                        nat.array, li, nat.h, nat.d, x, mids[0], ch.lookup_query if li == last else ch.lookup_node,
+                        ch.cseg, plan.zs_t, plan.cov_factors, i, plan.edit_weight, L - i, backups[li], w.data, plan.dual_ws,
                         solve_lam(plan), next_ln, last=li == last)
                 finally:
                     _touch(w)

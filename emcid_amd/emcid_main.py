@@ -257,20 +257,31 @@ def _read_threads() -> int:
     return max(1, min(8, effective_cpu_count() // 2))
 
 
-def _native_vstar_rows(names: Sequence[Optional[str]], width: int, pin: bool):
+def _vstar_file_rows(hparams) -> int:
+    """Rows per v* cache file: num_edit_tokens under ``use_new_compute_z`` (files (k, hidden), reference :946-957), else 1."""
+    k = int(getattr(hparams, "num_edit_tokens", 1) or 1)
+    return k if bool(getattr(hparams, "use_new_compute_z", False)) and k > 1 else 1
+
+
+def _native_vstar_rows(names: Sequence[Optional[str]], width: int, pin: bool, k: int = 1):
     """All cache files in one native call (csrc/host_io.cpp: a few threads, open/read/parse straight into the row buffer —
-    page-locked when the rows go to a GPU next, so the upload needs no staging copy).  Returns (rows (N, width) fp32 tensor,
-    status uint8 array: 0 = row read, 1 = no such file, 2 = a file for numpy), or None without the host library."""
+    page-locked when the rows go to a GPU next, so the upload needs no staging copy).  Returns (rows (N, width) fp32 tensor —
+    (N, k, width) for files of k > 1 rows —, status uint8 array: 0 = file read, 1 = no such file, 2 = a file for numpy), or None
+    without the host library."""
     from . import host_text
     if os.environ.get("EMCID_NATIVE_VSTAR", "1") == "0" or not host_text.available() or any(n is None for n in names):
         return None
     lib = host_text.load()
     n = len(names)
     blob, off = host_text.pack_strings(names)
-    rows = torch.empty((n, width), dtype=torch.float32, pin_memory=bool(pin))
+    rows = torch.empty((n, width) if k == 1 else (n, k, width), dtype=torch.float32, pin_memory=bool(pin))
     status = np.empty(n, dtype=np.uint8)
-    rc = lib.emcid_read_npz_rows_f32(blob, off.ctypes.data, n, b"v_star", width, rows.data_ptr(), width,
-                                     status.ctypes.data, _read_threads())
+    if k == 1:
+        rc = lib.emcid_read_npz_rows_f32(blob, off.ctypes.data, n, b"v_star", width, rows.data_ptr(), width,
+                                         status.ctypes.data, _read_threads())
+    else:
+        rc = lib.emcid_read_npz_rows_k_f32(blob, off.ctypes.data, n, b"v_star", k, width, rows.data_ptr(), k * width,
+                                           status.ctypes.data, _read_threads())
     if rc < 0:
         return None
     return rows, status
@@ -285,14 +296,13 @@ def load_v_stars(requests: Sequence[Dict], hparams, cache_name: Optional[str], s
     file :903-904, Stage 1 on a miss :905-969).  ``native``: (rows, status) of a native batch read of these very names that has
     already been made (the early reader's), so that a miss does not read the hits a second time."""
     names = [vstar_cache_name(cache_name, request, hparams, idx, suffix) for idx, request in enumerate(requests)]
+    k_file = _vstar_file_rows(hparams)
     if native is None:
-        native = _native_vstar_rows(names, int(width), pin) if (width and cache_name is not None and len(names)) else None
-    new_z = bool(getattr(hparams, "use_new_compute_z", False))
-    k_tok = int(getattr(hparams, "num_edit_tokens", 1) or 1)
-    if native is not None and not native[1].any() and not (new_z and k_tok > 1):
-        # every file was read natively: (width,) or (1, width) rows, which is all a one-token edit can hold — a k-token edit's
-        # files are (k, width) and take the per-file path below with its shape check (the native reader does not serve them)
-        return native[0]
+        native = _native_vstar_rows(names, int(width), pin, k_file) if (width and cache_name is not None and len(names)) else None
+    if native is not None and not native[1].any():
+        # every file was read natively: (width,) or (1, width) rows, or — use_new_compute_z with k > 1 — (k, width) files, whose
+        # stack flattens to the reference's "rq num" row order (:972-975)
+        return native[0].reshape(-1, native[0].shape[-1])
     rows: List[Optional[np.ndarray]] = [None] * len(requests)
     missing: List[int] = []
     for idx, request in enumerate(requests):
@@ -416,7 +426,7 @@ class _EarlyVstars:
     unedited leading layers: the reader is one ctypes call that does not hold the interpreter lock, so it runs beside the host's
     remaining preparation and is (nearly) done when the first solve asks — with the GPU twice as fast as in round 3 the read had
     moved onto the critical path (profiles/r04_g_call_events.txt: the host reached the first solve 0.2 ms before the device).
-    Anything the native reader does not serve (a miss, a file for numpy, k-token files) falls back to load_v_stars at result().
+    Anything the native reader does not serve (a miss, a file for numpy) falls back to load_v_stars at result().
     The rows are a SNAPSHOT of the files as they are when ``prepare`` runs: a plan prepared early and run after its cache files were
     rewritten edits towards the old targets (the lazy reader, EMCID_EARLY_VSTAR=0, reads at the first solve)."""
 
@@ -429,8 +439,6 @@ class _EarlyVstars:
         if (not width or cache_name is None or not len(requests) or os.environ.get("EMCID_NATIVE_VSTAR", "1") == "0"
                 or os.environ.get("EMCID_EARLY_VSTAR", "1") == "0" or not host_text.available()):
             return None
-        if bool(getattr(hparams, "use_new_compute_z", False)) and int(getattr(hparams, "num_edit_tokens", 1) or 1) > 1:
-            return None
         names = [vstar_cache_name(cache_name, request, hparams, idx, suffix) for idx, request in enumerate(requests)]
         if any(n is None for n in names):
             return None
@@ -441,7 +449,8 @@ class _EarlyVstars:
         lib = host_text.load()
         n = len(names)
         blob, off = host_text.pack_strings(names)
-        rows = torch.empty((n, int(width)), dtype=torch.float32, pin_memory=bool(pin))
+        k = _vstar_file_rows(hparams)        # (k, width) files of use_new_compute_z: the rows of file i at rows[i], "rq num" order
+        rows = torch.empty((n, int(width)) if k == 1 else (n, k, int(width)), dtype=torch.float32, pin_memory=bool(pin))
         status = np.empty(n, dtype=np.uint8)
         threads = _read_threads()
 
@@ -451,8 +460,8 @@ class _EarlyVstars:
             # (the buffers belong to this task, not to the object that waits for it: a plan that is dropped unrun must not free
             #  memory the reader is still writing)
             times[1] = time.perf_counter()
-            rc = lib.emcid_read_npz_rows_f32(blob, off.ctypes.data, n, b"v_star", int(width), rows.data_ptr(), int(width),
-                                             status.ctypes.data, threads)
+            rc = lib.emcid_read_npz_rows_k_f32(blob, off.ctypes.data, n, b"v_star", k, int(width), rows.data_ptr(), k * int(width),
+                                               status.ctypes.data, threads)
             times[2] = time.perf_counter()
             return rc
 
@@ -477,7 +486,7 @@ class _EarlyVstars:
     def result(self):
         rc = self.wait()
         if rc is not None and rc >= 0 and not self.keep[2].any():
-            return self.rows
+            return self.rows.reshape(-1, self.rows.shape[-1])
         # a miss or a file for numpy: the rows the batch read did serve are handed on (no second read of 999 hits for one miss)
         native = (self.rows, self.keep[2]) if rc is not None and rc >= 0 else None
         return load_v_stars(*self.args, **self.kwargs, native=native)

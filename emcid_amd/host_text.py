@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 _LIB = None
 _LOCK = threading.Lock()
 
@@ -54,6 +54,8 @@ def load():
         lib.emcid_find_token_ranges_idx.argtypes = [P, I64, I64, P, P, P, I64, P, P, P, I64, ctypes.c_int, ctypes.c_char_p, P, P, P]
         lib.emcid_trie_build.restype = P
         lib.emcid_trie_build.argtypes = [P, I64, I64, P, I64]
+        lib.emcid_trie_build_leaves.restype = P
+        lib.emcid_trie_build_leaves.argtypes = [P, I64, I64, P, I64, P, I64, I64]
         lib.emcid_trie_sizes.restype = None
         lib.emcid_trie_sizes.argtypes = [P, P, P, P, P]
         lib.emcid_trie_packed_bytes.restype = I64
@@ -64,6 +66,8 @@ def load():
         lib.emcid_trie_destroy.argtypes = [P]
         lib.emcid_read_npz_rows_f32.restype = I64
         lib.emcid_read_npz_rows_f32.argtypes = [ctypes.c_char_p, P, I64, ctypes.c_char_p, I64, P, I64, P, I32]
+        lib.emcid_read_npz_rows_k_f32.restype = I64
+        lib.emcid_read_npz_rows_k_f32.argtypes = [ctypes.c_char_p, P, I64, ctypes.c_char_p, I64, I64, P, I64, P, I32]
         if lib.emcid_host_abi_version() != ABI_VERSION:
             raise RuntimeError(f"{path}: ABI {lib.emcid_host_abi_version()}, this package needs {ABI_VERSION}; rebuild")
         _LIB = lib
@@ -306,14 +310,25 @@ def find_token_ranges(ids: np.ndarray, piece_ns: bytes, piece_off: np.ndarray, p
     return first, last, status
 
 
-def build_trie_packed(ids: np.ndarray, lookup: np.ndarray, bucket: int, alloc):
+def build_trie_packed(ids: np.ndarray, lookup: np.ndarray, bucket: int, alloc, eos: Optional[np.ndarray] = None,
+                      pad_token: int = 0):
     """``emcid_trie_build`` + ``emcid_trie_export``: ``alloc(nbytes)`` returns (object, address) of a host buffer (pinned, for an
-    asynchronous upload); returns (object, dict(U, n_real, dmax, R_pad, n)).  Layout: include/emcid_host.h."""
+    asynchronous upload); returns (object, dict(U, n_real, dmax, R_pad, n)).  Layout: include/emcid_host.h.
+    ``eos`` given: ``emcid_trie_build_leaves`` with ``lookup`` (n, k) — chains through each prompt's EOS, query-only leaves
+    behind it (``n`` is then n k, and the image carries the position array)."""
     lib = load()
     ids = np.ascontiguousarray(ids, dtype=np.int64)
     lookup = np.ascontiguousarray(lookup, dtype=np.int64)
     n, S = ids.shape
-    h = lib.emcid_trie_build(_ptr(ids), n, S, _ptr(lookup), int(bucket))
+    if eos is not None:
+        eos = np.ascontiguousarray(eos, dtype=np.int64)
+        k = lookup.shape[1] if lookup.ndim == 2 else 1
+        if lookup.size != n * k or eos.size != n:
+            raise ValueError("lookup must be (n, k) and eos (n,)")
+        h = lib.emcid_trie_build_leaves(_ptr(ids), n, S, _ptr(lookup), k, _ptr(eos), int(pad_token), int(bucket))
+        n = n * k
+    else:
+        h = lib.emcid_trie_build(_ptr(ids), n, S, _ptr(lookup), int(bucket))
     if not h:
         raise RuntimeError((lib.emcid_host_last_error() or b"").decode())
     try:

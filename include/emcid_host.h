@@ -88,6 +88,17 @@ int64_t emcid_trie_packed_bytes(const emcid_trie* t);
 int emcid_trie_export(const emcid_trie* t, void* out, int64_t out_bytes);
 void emcid_trie_destroy(emcid_trie* t);
 
+/* The trie of a num_edit_tokens = k > 1 edit (reference compute_z.py:2329-2382: rows [last subject token, EOS, EOS + 1, ...,
+ * EOS + k - 2] of prompts padded behind their EOS).  ids: n x S (>= 0), every row read through eos[i] (in [0, S)); lookup: n x k
+ * positions per prompt.  Each prompt's chain runs through its EOS.  A lookup at or before the EOS is the chain's node at that
+ * position; one behind it, at EOS + j, is a query-only LEAF: token = pad_token, depth = the EOS node's depth (depth is the
+ * length of the attention chain: a padding query attends to keys 0 .. EOS under the attention mask), ancestor chain = the
+ * EOS node's own row, own position = EOS + j.  Leaves are deduplicated by (EOS node, j) and numbered after every chain node in
+ * that order, before the padding nodes.  lookup_node / lookup_in_query have n k entries (row-major n x k).  The packed image
+ * of emcid_trie_export carries one more array behind anc: int32 position[U] (= depth on every node that is not a leaf). */
+emcid_trie* emcid_trie_build_leaves(const int64_t* ids, int64_t n, int64_t S, const int64_t* lookup, int64_t k, const int64_t* eos,
+                                    int64_t pad_token, int64_t bucket);
+
 /* The v* rows of an edit straight from the reference's cache files (emcid/emcid_main.py:885-899 reads them with np.load, one
  * per request; :951-968 writes them with np.savez(f, v_star=...)).  File i is paths[off[i] .. off[i+1]); each is read whole
  * and accepted when its FIRST zip member is "<member>.npy", stored uncompressed, dtype <f4 or <f8, shape (width,) or
@@ -97,6 +108,12 @@ void emcid_trie_destroy(emcid_trie* t);
  * Returns the number of rows with status != 0, or -1 on a bad argument.  `out` may be page-locked memory. */
 int64_t emcid_read_npz_rows_f32(const char* paths, const int64_t* off, int64_t n, const char* member, int64_t width, float* out,
                                 int64_t ld, uint8_t* status, int32_t n_threads);
+
+/* emcid_read_npz_rows_f32 for files of `rows` rows each: shape (rows, width), C order (the (num_edit_tokens, hidden) v* files of
+ * use_new_compute_z, reference emcid_main.py:946-957); rows == 1 also takes (width,).  File i goes to out[i * ld ..
+ * i * ld + rows * width), row-major: the stack "rq num" order of the reference's zs (:972-975).  ld >= rows * width. */
+int64_t emcid_read_npz_rows_k_f32(const char* paths, const int64_t* off, int64_t n, const char* member, int64_t rows, int64_t width,
+                                  float* out, int64_t ld, uint8_t* status, int32_t n_threads);
 
 const char* emcid_host_last_error(void);
 
