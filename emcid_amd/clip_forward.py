@@ -657,18 +657,6 @@ def _build_trie_leaves_numpy(tok: np.ndarray, lk: np.ndarray, device, bucket: in
                      position=torch.from_numpy(position).to(device), max_position=int(position.max()))
 
 
-class tuned_gemms:
-    """(Rounds 2-3 routed torch's fp32 GEMMs through TunableOp's table here; the projections run on the library's own kernels
-    since round 3 and the `EMCID_OWN_GEMM=0` comparison path takes torch's default selection: a no-op context, kept so that
-    the two forward drivers read the same.)"""
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
-
 def build_trie_packed(seqs: Sequence[Sequence[int]], device, bucket: int = ROW_BUCKET, return_nodes: bool = False):
     """Trie over WHOLE token sequences (Stage 0: every attended token of every caption is a lookup), built level by level
     with numpy — the Python loop of ``build_trie`` costs ~1 us per token, too slow for millions of caption tokens.
@@ -821,15 +809,10 @@ def run_layers(graph: ClipTextGraph, trie: TokenTrie, upto: int, on_fc2=None, la
     """Layers 0..upto (inclusive).  ``on_fc2(i, x, out) -> out'`` is called with the fc2 input/output of every layer
     (rows = all nodes, or the query rows at layer ``upto`` when ``last_rows_only``); whatever it returns is used
     as fc2's output.  Returns the residual stream after layer ``upto`` (query rows only if ``last_rows_only``)."""
-    cb = None
-    if on_fc2 is not None:
-        def cb(i, xs, outs):
-            out = on_fc2(i, xs[0], outs[0])
-            return None if out is None else [out]
-    res = run_layers_multi(graph, [trie], None, 0, upto, cb, last_rows_only, fc2_by_callback)
+    res = run_layers_from(graph, trie, None, 0, upto, on_fc2, last_rows_only, fc2_by_callback)
     if graph.guard is not None:
         graph.guard.flush()
-    return None if res is None else res[0][0]
+    return None if res is None else res[0]
 
 
 def run_prefix(graph: ClipTextGraph, trie: TokenTrie, stop: int):
@@ -849,34 +832,33 @@ def _run_prefix(graph: ClipTextGraph, trie: TokenTrie, stop: int):
         # (a leaf behind the EOS past the position table: refused here, on the host, like HF's CLIP embeddings)
         raise ValueError(f"Sequence length must be less than max_position_embeddings (position {trie.max_position} of "
                          f"{graph.position_embedding.num_embeddings})")
-    with tuned_gemms():
-        ln0 = graph.layers[0].ln1 if stop > 0 and graph.layers else None
-        te, pe = graph.token_embedding, graph.position_embedding
-        if ln0 is not None and _fusable(ln0) and te.weight.is_cuda and te.weight.dtype == torch.float32 \
-                and te.weight.stride(1) == 1 and pe.weight.stride(1) == 1 and te.padding_idx is None and te.max_norm is None \
-                and pe.max_norm is None and trie.position.dtype == torch.int32 and trie.token.dtype == torch.int64 \
-                and 0 <= trie.max_token < te.num_embeddings and trie.max_position < pe.num_embeddings:
-            # embeddings + the first layer's LN1 in one launch; token and position ranges are checked on the host copies
-            # (anything out of range takes the torch path, which raises like the reference's forward)
-            sp0 = graph.layers[0].split_of("qkv") if graph.layers[0].qkv_w is not None else None
-            if sp0 is not None and _sp_ln_ok(ln0):
-                hs, x_ln1 = hip.embed_layernorm_sp(te.weight, pe.weight, trie.token, trie.position, ln0)
-                nat = native_of(graph, trie, 0, stop)
-                if nat is not None:
-                    # every layer of the prefix in ONE C call (csrc/clip_layers.hip), in place on hs / the LN1 planes
-                    nxt = graph.layers[stop].ln1 if stop < len(graph.layers) else None
-                    if nxt is not None and not (_fusable(nxt) and _sp_ln_ok(nxt) and graph.layers[stop].split_of("qkv") is not None):
-                        nxt = None
-                    hip.clip_layers(nat.array, 0, stop, hs.shape[0], nat.h, nat.d, nat.heads, nat.scale, trie.anc, trie.depth,
-                                    hs, x_ln1, nxt)
-                    LAST_PATHS["native_layers"] += stop
-                    return hs, (x_ln1 if nxt is not None else None)
-            else:
-                hs, x_ln1 = hip.embed_layernorm(te.weight, pe.weight, trie.token, trie.position, ln0)
+    ln0 = graph.layers[0].ln1 if stop > 0 and graph.layers else None
+    te, pe = graph.token_embedding, graph.position_embedding
+    if ln0 is not None and _fusable(ln0) and te.weight.is_cuda and te.weight.dtype == torch.float32 \
+            and te.weight.stride(1) == 1 and pe.weight.stride(1) == 1 and te.padding_idx is None and te.max_norm is None \
+            and pe.max_norm is None and trie.position.dtype == torch.int32 and trie.token.dtype == torch.int64 \
+            and 0 <= trie.max_token < te.num_embeddings and trie.max_position < pe.num_embeddings:
+        # embeddings + the first layer's LN1 in one launch; token and position ranges are checked on the host copies
+        # (anything out of range takes the torch path, which raises like the reference's forward)
+        sp0 = graph.layers[0].split_of("qkv") if graph.layers[0].qkv_w is not None else None
+        if sp0 is not None and _sp_ln_ok(ln0):
+            hs, x_ln1 = hip.embed_layernorm_sp(te.weight, pe.weight, trie.token, trie.position, ln0)
+            nat = native_of(graph, trie, 0, stop)
+            if nat is not None:
+                # every layer of the prefix in ONE C call (csrc/clip_layers.hip), in place on hs / the LN1 planes
+                nxt = graph.layers[stop].ln1 if stop < len(graph.layers) else None
+                if nxt is not None and not (_fusable(nxt) and _sp_ln_ok(nxt) and graph.layers[stop].split_of("qkv") is not None):
+                    nxt = None
+                hip.clip_layers(nat.array, 0, stop, hs.shape[0], nat.h, nat.d, nat.heads, nat.scale, trie.anc, trie.depth,
+                                hs, x_ln1, nxt)
+                LAST_PATHS["native_layers"] += stop
+                return hs, (x_ln1 if nxt is not None else None)
         else:
-            hs, x_ln1 = embed(graph, trie), None
-        for i in range(stop):
-            hs, x_ln1 = _layer_full(graph, i, trie, hs, x_ln1, stop)
+            hs, x_ln1 = hip.embed_layernorm(te.weight, pe.weight, trie.token, trie.position, ln0)
+    else:
+        hs, x_ln1 = embed(graph, trie), None
+    for i in range(stop):
+        hs, x_ln1 = _layer_full(graph, i, trie, hs, x_ln1, stop)
     return hs, x_ln1
 
 
@@ -902,90 +884,74 @@ def _layer_full(graph, i, trie, hs, x_ln1, n_layers_needed):
     return mid + out, None
 
 
-def run_layers_multi(graph: ClipTextGraph, tries: Sequence[TokenTrie], states, start: int, upto: int, on_fc2=None,
-                     last_rows_only: bool = True, fc2_by_callback=(), callback_adds_residual: bool = False,
-                     split_aware: bool = False):
-    """Layers start..upto (inclusive) for several tries at once, layer by layer: the prompt list of an edit may arrive in
-    slices (compute_z.iter_prompt_chunks), each with its own trie; rows of different slices never attend to each other,
-    but an edited layer's solve needs the keys of all of them before any slice can go on.  ``states[c]``: (residual
-    stream, LN1 of it | None) of slice c entering layer ``start`` (None: start from the embeddings, start == 0).
-    ``on_fc2(i, xs, outs) -> outs'``: lists over the slices (``split_aware``: the fc2 inputs may arrive as ``hip.SplitRows``
-    with their fp32 twins — the edit engine feeds the planes to fc2 and gathers the keys from the twin; otherwise the callback
-    gets plain fp32 tensors).  Returns the list of final states, or None if the callback ended the pass."""
+def _tail_ln(graph: ClipTextGraph, i: int, nxt):
+    """The next layer's LN1 when the native fc2 tail can produce it as planes (None: it is computed separately)."""
+    return nxt if nxt is not None and _fusable(nxt) and _sp_ln_ok(nxt) and \
+        graph.layers[i + 1].qkv_w is not None and graph.layers[i + 1].split_of("qkv") is not None else None
+
+
+def run_layers_from(graph: ClipTextGraph, trie: TokenTrie, state, start: int, upto: int, on_fc2=None,
+                    last_rows_only: bool = True, fc2_by_callback=(), edit_callback: bool = False):
+    """Layers start..upto (inclusive).  ``state``: (residual stream, LN1 of it | None) entering layer ``start`` (None: start
+    from the embeddings, start == 0).  ``on_fc2(i, x, out) -> out'`` gets plain fp32 fc2 inputs.  ``edit_callback`` (the edit
+    engine): ``on_fc2(i, x, out, mid, next_ln)`` instead, where ``x`` may be a ``hip.SplitRows`` with its fp32 twin (the engine
+    feeds the planes to fc2 and gathers the keys from the twin) and ``mid`` is the residual stream: for a layer in
+    ``fc2_by_callback`` it returns fc2(x) + mid, or the pair (hs, LN1 planes of the next layer) when it also took that LayerNorm
+    (``next_ln``: that LayerNorm, or None) off our hands.  Returns the final state, or None if the callback ended the pass."""
     _check_fp32(graph)
     by_cb = set(fc2_by_callback)
-    with tuned_gemms():
-        if states is None:
-            states = [(embed(graph, t), None) for t in tries]
-        states = list(states)
-        for i in range(start, upto + 1):
-            layer = graph.layers[i]
-            xs, mids = [], []
-            nats = []
-            for trie, (hs, x_ln1) in zip(tries, states):
-                rows = trie.query_rows if (last_rows_only and i == upto) else None
-                nat = native_of(graph, trie, i, i + 1) if isinstance(x_ln1, hip.SplitRows) else None
-                nats.append(nat)
-                if nat is not None:
-                    # attention block + fc1 in ONE C call (csrc/clip_layers.hip)
-                    mid, x = hip.clip_layer_head(nat.array, i, hs.shape[0], nat.h, nat.d, nat.heads, nat.scale, trie.anc,
-                                                 trie.depth, rows, hs, x_ln1, want_f32=on_fc2 is not None)
-                    LAST_PATHS["native_layers"] += 1
-                    xs.append(x)
-                    mids.append(mid)
-                    continue
-                mid, ln2_mid = layer_attention_block(layer, hs, trie, rows, x_ln1)
-                xs.append(mlp_hidden(layer, ln2_mid, want_f32=on_fc2 is not None))
-                mids.append(mid)
-            # layers in ``fc2_by_callback``: the callback produces fc2's output itself (out is passed as None), so an
-            # edited layer's projection is computed once, with the new weight, instead of twice.  With ``callback_adds_residual``
-            # the callback gets the residual streams too and returns fc2(x) + mid (the add in its GEMM's epilogue).
-            nxt = graph.layers[i + 1].ln1 if i < upto else None
-            summed = False
-            tail_states = None
-            if i in by_cb or not OWN_GEMM:
-                outs = [None if i in by_cb else layer.fc2(x.float() if isinstance(x, hip.SplitRows) else x) for x in xs]
-            elif on_fc2 is None and all(nat is not None for nat in nats):
-                # fc2 + residual add + the next layer's LN1 in ONE C call
-                nl = nxt if nxt is not None and _fusable(nxt) and _sp_ln_ok(nxt) and \
-                    graph.layers[i + 1].qkv_w is not None and graph.layers[i + 1].split_of("qkv") is not None else None
-                tail_states = [hip.clip_layer_tail(nat.array, i, nat.h, nat.d, x, mid, nl) for nat, x, mid in zip(nats, xs, mids)]
-                if nl is None and nxt is not None:
-                    tail_states = [(hs, _next_ln1(graph, i + 1, hs, nxt)) for hs, _ in tail_states]
-                outs = [hs for hs, _ in tail_states]
-                summed = True
+    hs, x_ln1 = (embed(graph, trie), None) if state is None else state
+    for i in range(start, upto + 1):
+        layer = graph.layers[i]
+        rows = trie.query_rows if (last_rows_only and i == upto) else None
+        nat = native_of(graph, trie, i, i + 1) if isinstance(x_ln1, hip.SplitRows) else None
+        if nat is not None:
+            # attention block + fc1 in ONE C call (csrc/clip_layers.hip)
+            mid, x = hip.clip_layer_head(nat.array, i, hs.shape[0], nat.h, nat.d, nat.heads, nat.scale, trie.anc,
+                                         trie.depth, rows, hs, x_ln1, want_f32=on_fc2 is not None)
+            LAST_PATHS["native_layers"] += 1
+        else:
+            mid, ln2_mid = layer_attention_block(layer, hs, trie, rows, x_ln1)
+            x = mlp_hidden(layer, ln2_mid, want_f32=on_fc2 is not None)
+        # layers in ``fc2_by_callback``: the callback produces fc2's output itself (out is passed as None), so an
+        # edited layer's projection is computed once, with the new weight, instead of twice
+        nxt = graph.layers[i + 1].ln1 if i < upto else None
+        summed = False
+        tail_state = None
+        if i in by_cb or not OWN_GEMM:
+            out = None if i in by_cb else layer.fc2(x.float() if isinstance(x, hip.SplitRows) else x)
+        elif on_fc2 is None and nat is not None:
+            # fc2 + residual add + the next layer's LN1 in ONE C call
+            nl = _tail_ln(graph, i, nxt)
+            tail_state = hip.clip_layer_tail(nat.array, i, nat.h, nat.d, x, mid, nl)
+            if nl is None and nxt is not None:
+                tail_state = (tail_state[0], _next_ln1(graph, i + 1, tail_state[0], nxt))
+            out = tail_state[0]
+            summed = True
+        else:
+            out = linear(x, layer.fc2.weight, layer.fc2.bias, residual=mid, wsp=layer.split_of("fc2"))
+            summed = True
+        if on_fc2 is not None:
+            if edit_callback and not summed:
+                nl = _tail_ln(graph, i, nxt)
+                out = on_fc2(i, x, out, mid, nl)
+                if isinstance(out, tuple):
+                    tail_state = (out[0], out[1] if nl is not None else _next_ln1(graph, i + 1, out[0], nxt))
+                    out = out[0]
+                summed = out is not None and i in by_cb
             else:
-                fsp = layer.split_of("fc2")
-                outs = [linear(x, layer.fc2.weight, layer.fc2.bias, residual=mid, wsp=fsp) for x, mid in zip(xs, mids)]
-                summed = True
-            if on_fc2 is not None:
-                cb_xs = xs if split_aware else [x.float() if isinstance(x, hip.SplitRows) else x for x in xs]
-                if callback_adds_residual and not summed:
-                    if split_aware:
-                        # a split-aware callback may also take the next layer's LN1 off our hands (fc2 + residual + LN1 in
-                        # one C call): it then returns (hs, LN1 planes) pairs instead of the fc2 outputs
-                        nl = nxt if nxt is not None and _fusable(nxt) and _sp_ln_ok(nxt) and \
-                            graph.layers[i + 1].qkv_w is not None and graph.layers[i + 1].split_of("qkv") is not None else None
-                        outs = on_fc2(i, cb_xs, outs, mids, nl)
-                        if outs is not None and len(outs) and isinstance(outs[0], tuple):
-                            tail_states = [(hs, x if nl is not None else _next_ln1(graph, i + 1, hs, nxt)) for hs, x in outs]
-                            outs = [hs for hs, _ in outs]
-                    else:
-                        outs = on_fc2(i, cb_xs, outs, mids)
-                    summed = outs is not None and i in by_cb
-                else:
-                    outs = on_fc2(i, cb_xs, outs)
-                if outs is None:
-                    return None
-            if tail_states is not None:
-                states = tail_states
-            elif summed:
-                states = [(hs, _next_ln1(graph, i + 1, hs, nxt)) for hs in outs]
-            elif nxt is not None and _fusable(nxt):
-                states = [hip.add_layernorm(mid, out, nxt) for mid, out in zip(mids, outs)]
-            else:
-                states = [(mid + out, None) for mid, out in zip(mids, outs)]
-    return states
+                out = on_fc2(i, x if edit_callback else (x.float() if isinstance(x, hip.SplitRows) else x), out)
+            if out is None:
+                return None
+        if tail_state is not None:
+            hs, x_ln1 = tail_state
+        elif summed:
+            hs, x_ln1 = out, _next_ln1(graph, i + 1, out, nxt)
+        elif nxt is not None and _fusable(nxt):
+            hs, x_ln1 = hip.add_layernorm(mid, out, nxt)
+        else:
+            hs, x_ln1 = mid + out, None
+    return hs, x_ln1
 
 
 def last_hidden_at_lookup(graph: ClipTextGraph, trie: TokenTrie) -> torch.Tensor:

@@ -157,7 +157,7 @@ def build_prompt_batch(tokenizer, requests: Sequence[Dict], device, finder: Opti
 
 @dataclass
 class PromptChunk:
-    """Host-side tokenization of a contiguous slice of the request list (prompts truncated behind the last lookup token)."""
+    """Host-side tokenization of the request list (prompts truncated behind the last lookup token)."""
     ids: np.ndarray          # (B_c, S_c) int64
     lookup: Sequence[int]    # position of the last subject token per prompt (list or int64 array)
     counts: List[int]        # prompts per request
@@ -308,40 +308,32 @@ def templated_prompt_chunk(tokenizer, requests: Sequence[Dict], first: Dict, def
     return PromptChunk(np.ascontiguousarray(ids[:, :int(lk.max()) + 1]), lk, counts, n, verify=verify, offsets=offsets)
 
 
-def iter_prompt_chunks(tokenizer, requests: Sequence[Dict], n_chunks: int, defer_probe: bool = False, num_edit_tokens: int = 1):
-    """The request list in ``n_chunks`` contiguous slices, each tokenized, searched and truncated on its own, lazily: the
-    caller builds a slice's prefix trie and launches its share of the encoder forward before asking for the next slice,
-    so the GPU works on slice i while the host tokenizes slice i+1 (no helper thread: the launches are asynchronous).
-    ``num_edit_tokens`` = k > 1: each row is kept through its EOS and the chunk carries (B, k) lookups and the EOS positions."""
+def prompt_chunk(tokenizer, requests: Sequence[Dict], defer_probe: bool = False, num_edit_tokens: int = 1) -> PromptChunk:
+    """The whole request list tokenized, searched and truncated: the templated fast path when it serves the requests, else every
+    prompt formatted, tokenized and searched as a string.  ``num_edit_tokens`` = k > 1: each row is kept through its EOS and the
+    chunk carries (B, k) lookups and the EOS positions."""
     k = int(num_edit_tokens)
     n = len(requests)
-    n_chunks = max(1, min(n_chunks, n))
     first = requests[0]
-    finder = finder_for(tokenizer)
-    for i in range(n_chunks):
-        lo, hi = (n * i) // n_chunks, (n * (i + 1)) // n_chunks
-        if os.environ.get("EMCID_TEMPLATED", "1") != "0":
-            fast = templated_prompt_chunk(tokenizer, requests[lo:hi], first, defer_probe, k)
-            if fast is not None:
-                yield fast
-                continue
-        prompts, subjects, counts = expand_request_prompts(requests[lo:hi], first)
-        enc = tokenize_lists(tokenizer, prompts)
-        ids = enc["input_ids"]
-        lookup = [r[-1] - 1 for r in finder.batch(ids, subjects)]
-        lk = np.asarray(lookup, dtype=np.int64)
-        bad = np.nonzero((lk < 0) | (lk >= ids.shape[1]))[0]
-        if bad.size:
-            j = int(bad[0])
-            raise ValueError(f"lookup index {lookup[j]} outside the padded prompt (S={ids.shape[1]}) for prompt {prompts[j]!r}")
-        if sum(counts) != len(prompts):
-            raise ValueError(f"request prompt counts ({sum(counts)}) do not cover the {len(prompts)} prompts")
-        if k > 1:
-            eos = np.asarray(enc["attention_mask"], dtype=np.int64).sum(axis=1) - 1
-            yield PromptChunk(np.ascontiguousarray(ids[:, :int(eos.max()) + 1]), multi_token_lookup(lk, eos, k), counts, hi - lo,
-                              eos=eos)
-            continue
-        yield PromptChunk(np.ascontiguousarray(ids[:, :int(lk.max()) + 1]), lookup, counts, hi - lo)
+    if os.environ.get("EMCID_TEMPLATED", "1") != "0":
+        fast = templated_prompt_chunk(tokenizer, requests, first, defer_probe, k)
+        if fast is not None:
+            return fast
+    prompts, subjects, counts = expand_request_prompts(requests)
+    enc = tokenize_lists(tokenizer, prompts)
+    ids = enc["input_ids"]
+    lookup = [r[-1] - 1 for r in finder_for(tokenizer).batch(ids, subjects)]
+    lk = np.asarray(lookup, dtype=np.int64)
+    bad = np.nonzero((lk < 0) | (lk >= ids.shape[1]))[0]
+    if bad.size:
+        j = int(bad[0])
+        raise ValueError(f"lookup index {lookup[j]} outside the padded prompt (S={ids.shape[1]}) for prompt {prompts[j]!r}")
+    if sum(counts) != len(prompts):
+        raise ValueError(f"request prompt counts ({sum(counts)}) do not cover the {len(prompts)} prompts")
+    if k > 1:
+        eos = np.asarray(enc["attention_mask"], dtype=np.int64).sum(axis=1) - 1
+        return PromptChunk(np.ascontiguousarray(ids[:, :int(eos.max()) + 1]), multi_token_lookup(lk, eos, k), counts, n, eos=eos)
+    return PromptChunk(np.ascontiguousarray(ids[:, :int(lk.max()) + 1]), lookup, counts, n)
 
 
 def gather_request_means(act: torch.Tensor, batch: PromptBatch) -> torch.Tensor:

@@ -35,7 +35,7 @@ import torch.nn.functional as F
 from . import hip
 from . import clip_forward
 from .clip_attention import hip_attention
-from .compute_z import PromptBatch, build_prompt_batch, build_prompt_batch_multi, gather_request_means, iter_prompt_chunks
+from .compute_z import PromptBatch, build_prompt_batch, build_prompt_batch_multi, gather_request_means, prompt_chunk
 from .nethook import StopForward, get_module, get_parameter
 
 
@@ -70,8 +70,8 @@ class LayerEdit:
 
 @dataclass
 class TrieChunk:
-    """One slice of this rank's requests on the prefix-trie forward: its trie, its request -> prompt offsets and, when
-    prepare already ran the unedited leading layers for it, the state that enters the first edited layer."""
+    """This rank's requests on the prefix-trie forward: their trie, the request -> prompt offsets and, when prepare already
+    ran the unedited leading layers, the state that enters the first edited layer."""
     trie: clip_forward.TokenTrie
     seg: torch.Tensor                      # (n_requests + 1,) int64 prompt offsets
     n_requests: int
@@ -132,7 +132,7 @@ class EncoderEditPlan:
     side_stream: Optional[torch.cuda.Stream] = None
     solver: str = "auto"                                 # "direct" | "dual" | "auto" (dual when N is well below d)
     graph: Optional[clip_forward.ClipTextGraph] = None   # set -> prefix-deduplicated forward (clip_forward.py)
-    chunks: Optional[List[TrieChunk]] = None             # the slices of the trie forward (None: hooked-HF forward)
+    chunk: Optional[TrieChunk] = None                    # the prompts on the trie forward (None: hooked-HF forward)
     tokenizer: object = None
     local_requests: Optional[List[Dict]] = None
     zs_pending: object = None
@@ -151,22 +151,34 @@ class EncoderEditPlan:
         return concept_bounds(self, r)
 
     @property
-    def trie(self):                        # the (first) trie of the prefix-deduplicated forward, None on the hooked-HF path
-        return self.chunks[0].trie if self.chunks and self.graph is not None else None
+    def trie(self):                        # the trie of the prefix-deduplicated forward, None on the hooked-HF path
+        return self.chunk.trie if self.chunk is not None and self.graph is not None else None
 
     @trie.setter
     def trie(self, value):                 # ``plan.graph = plan.trie = None`` switches a plan to the hooked-HF forward
         if value is not None:
-            raise AttributeError("assign plan.chunks instead")
-        self.chunks = None
+            raise AttributeError("assign plan.chunk instead")
+        self.chunk = None
+
+    @property
+    def chunks(self) -> Optional[List[TrieChunk]]:       # (read-only, for reports that count prompt slices: always one)
+        return None if self.chunk is None else [self.chunk]
 
     @property
     def n_prompts(self) -> int:
-        return sum(c.n_prompts for c in self.chunks) if self.chunks else self.ensure_batch().n_prompts
+        return self.chunk.n_prompts if self.chunk is not None else self.ensure_batch().n_prompts
 
     @property
     def trie_rows(self):
-        return (sum(c.trie.n_nodes for c in self.chunks), sum(c.trie.n_tokens_dense for c in self.chunks)) if self.chunks else None
+        return (self.chunk.trie.n_nodes, self.chunk.trie.n_tokens_dense) if self.chunk is not None else None
+
+    def restore_weights(self):
+        """Put the edited weights back to the values they had before the last run (W0, kept in ``backups``)."""
+        if self.backups is None:
+            return
+        with torch.no_grad():
+            for l, w0 in self.backups.items():
+                get_parameter(self.text_encoder, self.weight_name(l)).copy_(w0)
 
     def resolve_targets(self) -> torch.Tensor:
         """(N, h) fp32 v* rows in HBM.  When prepare was handed the reader thread's future, this is where it is joined:
@@ -230,7 +242,7 @@ def _workspace(kind: str, N: int, d: int, h: int, dev, plan):
             if holder is None and free is None:
                 free = ws
         if free is None:
-            free = {"dual": hip.DualWorkspace, "lu": hip.LuWorkspace}.get(kind, hip.EditWorkspace)(N, d, h, dev)
+            free = hip.DualWorkspace(N, d, h, dev) if kind == "dual" else hip.EditWorkspace(N, d, h, dev, lu=kind == "lu")
             if len(pool) < WS_PER_SHAPE:      # beyond that the workspace lives as long as its plan
                 pool.append(free)
         free.lease = weakref.ref(plan)
@@ -264,16 +276,7 @@ def factor_cache_key(covs: Sequence[torch.Tensor], lam: float, edit_weight: floa
     identity and version counter of the HBM-resident C tensors (the entries of emcid_main's covariance cache).
     Reusing a factor across lam changes the weights at fp64-rounding level against a process that factors lam C' itself;
     (A process that wants bit-stable output across runs keeps lam fixed.)"""
-    key_lam = None
-    key_ew = float(edit_weight)
-    return (tuple((c.device.index, c.data_ptr(), c._version, tuple(c.shape)) for c in covs), key_ew, key_lam)
-
-
-def solve_lam(plan) -> float:
-    """The lam handed to the dual stages.  (The cached factors are keyed by the statistics AND edit_weight, so they always belong
-    to this call's edit_weight; round 4's EMCID_EDIT_WEIGHT_SCALAR switch — reuse them across edit_weights by treating C' as a
-    scalar multiple of C — left the 1e-4 bar on statistics of condition > 1e5 and is gone.)"""
-    return plan.lam
+    return (tuple((c.device.index, c.data_ptr(), c._version, tuple(c.shape)) for c in covs), float(edit_weight))
 
 
 def clear_engine_caches():
@@ -309,14 +312,31 @@ def _solver_mode(plan) -> str:
     return SOLVER or os.environ.get("EMCID_SOLVER") or plan.solver
 
 
-def _use_dual(plan, d: int) -> bool:
+DUAL_FORMS = ("dual", "dual_apply", "dual_cols")
+
+
+def solver_form(plan, d: int, keep_factors: bool) -> str:
+    """Which closed form solves every edited layer of a run:
+      "direct"       A = lam C' + K^T K (d x d) factored and solved (edit_layer), optionally keeping adj_k and resid
+      "direct_rows"  the same, sharded: every rank factors A, the solves and dW are split by concept rows (edit_layer_shard)
+      "lu"           the reference's LU with partial pivoting, the fallback after a failed Cholesky (edit_layer_lu)
+      "dual"         the Woodbury form on the factors of lam C' (N x N systems), adj_k and resid kept (edit_layer_dual)
+      "dual_apply"   the Woodbury form that only writes the new weights (edit_layer_dual_apply)
+      "dual_cols"    dual_apply split by 128-wide column tiles of d over the ranks (edit_layer_dual_cols)"""
     mode = _solver_mode(plan)
-    if mode == "dual":
-        return True
-    if mode in ("direct", "lu"):
-        return False
-    np_, dp = -(-plan.n_total // hip.NB) * hip.NB, -(-d // hip.NB) * hip.NB
-    return np_ * 5 <= dp * 3      # N x N system + two extra solves pay off when N is well below d
+    if mode == "lu":
+        return "lu"
+    if mode in ("dual", "direct"):
+        dual = mode == "dual"
+    else:
+        np_, dp = -(-plan.n_total // hip.NB) * hip.NB, -(-d // hip.NB) * hip.NB
+        dual = np_ * 5 <= dp * 3      # N x N system + two extra solves pay off when N is well below d
+    if dual:
+        if keep_factors:
+            return "dual"
+        # (fewer 128-column tiles than ranks: every rank runs the whole layer itself)
+        return "dual_cols" if plan.shard.collective and -(-d // hip.NB) >= plan.shard.world else "dual_apply"
+    return "direct_rows" if plan.shard.collective and not keep_factors else "direct"
 
 
 def prepare_encoder_edit(text_encoder, tokenizer, requests: Sequence[Dict], layers, rewrite_module_tmp, lam,
@@ -357,65 +377,57 @@ def prepare_encoder_edit(text_encoder, tokenizer, requests: Sequence[Dict], laye
                            None, covs, len(requests) * k, shard, tokenizer=tokenizer, local_requests=local, num_edit_tokens=k)
     if graph is not None:
         # As soon as the prompts are tokenized their prefix trie is built and the unedited leading layers are LAUNCHED here,
-        # so the GPU runs them underneath the rest of the host preparation (v* reads, statistics lookups).  The prompt list
-        # could also be cut into slices (iter_prompt_chunks takes a count), each launched before the next is tokenized; measured on 2 x EPYC
-        # 9575F (scripts/host_profile.py, configurations interleaved) every extra tokenizer call costs 3-4 ms of fixed
-        # overhead (waking the backend's thread pool), more than the 2.9 ms of GPU time a second slice hides: default 1.
-        n_chunks = 1
+        # so the GPU runs them underneath the rest of the host preparation (v* reads, statistics lookups).  (Cutting the prompt
+        # list into slices, each launched before the next is tokenized, measured slower on 2 x EPYC 9575F: every extra tokenizer
+        # call costs 3-4 ms of fixed overhead, waking the backend's thread pool, more than the 2.9 ms of GPU time a second
+        # slice hides.)
         first_edit = plan.layers[0]
-        chunks: List[TrieChunk] = []
         try:
             # (k > 1: every check of the tokenization up front — a restarted preparation on one rank would pair its collective
             # with another rank's next one)
-            it = iter_prompt_chunks(tokenizer, local, n_chunks, defer_probe=_defer_checks and k == 1, num_edit_tokens=k)
-            while True:
+            with phase("tokenize+lookup"):
+                pc = prompt_chunk(tokenizer, local, defer_probe=_defer_checks and k == 1, num_edit_tokens=k)
+            if k > 1:
+                _check_padded_length(shard, int(pc.eos.max()) + 1, k, graph.position_embedding.num_embeddings, device)
+                length_checked = True
+                with phase("trie"):
+                    pad = getattr(tokenizer, "pad_token_id", None)
+                    if pad is None and k > 2:
+                        raise ValueError("num_edit_tokens > 2 pads the prompts: the tokenizer has no pad token")
+                    perm, cseg = concept_segments(pc.counts, k)
+                    offs = pc.request_offsets()
+                    trie = clip_forward.build_trie(pc.ids, pc.lookup, device, tail=np.concatenate([offs, cseg, perm]),
+                                                   eos=pc.eos, pad_token=int(pad or 0))
+                    n1, n2 = offs.size, offs.size + cseg.size
+                    seg, cseg_d, perm_d = trie.tail[:n1], trie.tail[n1:n2], trie.tail[n2:]
+                    chunk = TrieChunk(trie, seg, pc.n_requests, len(pc.lookup), None, trie.lookup_node.index_select(0, perm_d),
+                                      trie.lookup_in_query.index_select(0, perm_d), cseg_d)
+            else:
+                with phase("trie"):
+                    trie = clip_forward.build_trie(pc.ids, pc.lookup, device, tail=pc.request_offsets())
+                    chunk = TrieChunk(trie, trie.tail, pc.n_requests, len(pc.lookup))
+            with phase("prefix launches"), torch.no_grad():
+                hs, x_ln1 = clip_forward.run_prefix(graph, trie, first_edit)
+            chunk.state = (first_edit, hs, x_ln1)
+            if pc.verify is not None:
+                # the checks of the templated tokenization that need not hold the first launch back — the native tokenizer's
+                # cross-check against the public tokenizer call, the reference's subject walk against the lookup positions
+                # known from the construction of the rows — run now that the GPU has the leading layers to work on.
+                # If one says no (a name that also occurs earlier in its prompt; a tokenizer disagreement retires the native
+                # twin for good), the preparation starts over with every check up front; what was launched is abandoned.
                 with phase("tokenize+lookup"):
-                    pc = next(it, None)
-                if pc is None:
-                    break
-                if k > 1:
-                    if not length_checked:
-                        _check_padded_length(shard, int(pc.eos.max()) + 1, k, graph.position_embedding.num_embeddings, device)
-                        length_checked = True
-                    with phase("trie"):
-                        pad = getattr(tokenizer, "pad_token_id", None)
-                        if pad is None and k > 2:
-                            raise ValueError("num_edit_tokens > 2 pads the prompts: the tokenizer has no pad token")
-                        perm, cseg = concept_segments(pc.counts, k)
-                        offs = pc.request_offsets()
-                        trie = clip_forward.build_trie(pc.ids, pc.lookup, device, tail=np.concatenate([offs, cseg, perm]),
-                                                       eos=pc.eos, pad_token=int(pad or 0))
-                        n1, n2 = offs.size, offs.size + cseg.size
-                        seg, cseg_d, perm_d = trie.tail[:n1], trie.tail[n1:n2], trie.tail[n2:]
-                        chunk = TrieChunk(trie, seg, pc.n_requests, len(pc.lookup), None, trie.lookup_node.index_select(0, perm_d),
-                                          trie.lookup_in_query.index_select(0, perm_d), cseg_d)
-                else:
-                    with phase("trie"):
-                        trie = clip_forward.build_trie(pc.ids, pc.lookup, device, tail=pc.request_offsets())
-                        chunk = TrieChunk(trie, trie.tail, pc.n_requests, len(pc.lookup))
-                with phase("prefix launches"), torch.no_grad():
-                    hs, x_ln1 = clip_forward.run_prefix(graph, trie, first_edit)
-                chunk.state = (first_edit, hs, x_ln1)
-                chunks.append(chunk)
-                if pc.verify is not None:
-                    # the checks of the templated tokenization that need not hold the first launch back — the native tokenizer's
-                    # cross-check against the public tokenizer call, the reference's subject walk against the lookup positions
-                    # known from the construction of the rows — run now that the GPU has this slice's leading layers to work on.
-                    # If one says no (a name that also occurs earlier in its prompt; a tokenizer disagreement retires the native
-                    # twin for good), the preparation starts over with every check up front; what was launched is abandoned.
-                    with phase("tokenize+lookup"):
-                        agreed = pc.verify()
-                    if not agreed:
-                        return prepare_encoder_edit(text_encoder, tokenizer, requests, layers, rewrite_module_tmp, lam, edit_weight,
-                                                    zs_t, covs, shard, layer_module_tmp, forward_mode, num_edit_tokens,
-                                                    _defer_checks=False)
-            plan.graph, plan.chunks = graph, chunks
+                    agreed = pc.verify()
+                if not agreed:
+                    return prepare_encoder_edit(text_encoder, tokenizer, requests, layers, rewrite_module_tmp, lam, edit_weight,
+                                                zs_t, covs, shard, layer_module_tmp, forward_mode, num_edit_tokens,
+                                                _defer_checks=False)
+            plan.graph, plan.chunk = graph, chunk
             # gauges (not counters): the trie of the last prepared call — rows run per layer and the tokens they stand for
             clip_forward.LAST_PATHS["last_trie_rows"], clip_forward.LAST_PATHS["last_trie_tokens"] = plan.trie_rows
         except (clip_forward.UnsupportedEncoder, IndexError) as e:
             clip_forward.note_fallback("prepare_encoder_edit (prompt batch)", e)
-            plan.graph = plan.chunks = None
-    if plan.chunks is None:
+            plan.graph = plan.chunk = None
+    if plan.chunk is None:
         with phase("tokenize+lookup"):
             batch = plan.ensure_batch()
         if not length_checked:
@@ -549,6 +561,75 @@ def _touch(w: torch.Tensor):
     torch.autograd.graph.increment_version(w)
 
 
+def _dual_factors(plan: EncoderEditPlan, form: str, dev):
+    """The factors of lam * C'_l of every edited layer for a dual form: L L^T, and the explicit inverses X_l = inv(L_l) that
+    turn a layer's two M-solves into two GEMMs.  Returns (fac_done, lazy): per edited layer the event its solve waits for
+    (None: the factors came from the cache, nothing to wait for), and whether the solve of layer i builds X of layer i + 1."""
+    L = len(plan.layers)
+    fkey = factor_cache_key([plan.covs[l] for l in plan.layers], plan.lam, plan.edit_weight)
+    with ENGINE_LOCK:
+        hit = _FACTOR_CACHE.get(fkey) if _factor_cache_size() > 0 and plan.lam > 0 else None
+        if hit is not None and not (hit[0].lam and hit[0].lam > 0):
+            hit = None
+        if hit is not None:
+            _FACTOR_CACHE.move_to_end(fkey)
+    if hit is not None:
+        # lam0 * C'_l = L L^T and X = inv(L) of every edited layer are already in HBM from an earlier edit with the
+        # same statistics and edit_weight (any lam0: the solve stages take lam / lam0): every M-solve of this pass is a
+        # GEMM against X, nothing is factored but the N x N systems
+        plan.cov_factors, plan.factors_from_cache = hit[0], True
+        if plan.cov_factors.ready is not None:
+            torch.cuda.current_stream(dev).wait_event(plan.cov_factors.ready)
+        return None, False
+    # lam * C'_l does not depend on the concepts: factor it for ALL edited layers in one batched pass on a side
+    # stream, underneath the encoder forward that produces the first layer's keys
+    if plan.side_stream is None:
+        # high priority: the factorization is a long chain of small dependent kernels; each must get the next
+        # free CU ahead of the forward's wide GEMMs or the chain stretches to several times its own length
+        plan.side_stream = torch.cuda.Stream(device=dev, priority=-1)
+    plan.side_stream.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(plan.side_stream):
+        if plan.cov_factors is not None and plan.cov_factors.cached:
+            plan.cov_factors = None        # never refactor into a workspace the cache hands to other edits
+        if plan.cov_factors is not None:
+            plan.cov_factors.info.zero_()
+        plan.cov_factors = hip.factor_cov([plan.covs[l] for l in plan.layers], plan.lam, plan.edit_weight,
+                                          plan.cov_factors, inverse=False)
+        plan.factor_key = fkey
+        chol_done = torch.cuda.Event()
+        chol_done.record(plan.side_stream)
+        fac_done = [chol_done] * L
+        # The first edited layer solves against M by block substitution with L as soon as the factorization is there.
+        # The apply-only form builds the explicit inverse of each LATER layer one layer ahead, on the side stream, exactly
+        # while the previous layer's solve sits in the latency-bound Cholesky of its N x N system (the chip is idle there).
+        # (Building them all right after the factorization, batched underneath the forward, cost the forward more than it
+        # hid: HISTORY.md §5.)  The other forms build them here in one batch; the column-sharded solve multiplies by X in
+        # every layer, the first one included.
+        lazy = form == "dual_apply" and L > 1
+        first_x = 0 if form == "dual_cols" else 1
+        if not lazy and first_x < L:
+            hip.cov_inverse(plan.cov_factors, first_x, L - first_x)
+            ev = torch.cuda.Event()
+            ev.record(plan.side_stream)
+            fac_done[first_x:] = [ev] * (L - first_x)
+    return fac_done, lazy
+
+
+def _finish_inverse_factors(plan: EncoderEditPlan, dev):
+    """After a pass that factored lam * C' itself: build the explicit inverse factors it did not need (off the critical path,
+    on the side stream) so that check_info can hand the complete set to later edits."""
+    if plan.factor_key is None or _factor_cache_size() <= 0:
+        return
+    missing = [i for i in range(len(plan.layers)) if i not in plan.cov_factors.have_inverse]
+    if missing:
+        plan.side_stream.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(plan.side_stream):
+            for i in missing:
+                hip.cov_inverse(plan.cov_factors, i, 1)
+            plan.cov_factors.ready = torch.cuda.Event()
+            plan.cov_factors.ready.record(plan.side_stream)
+
+
 def run_encoder_edit(plan: EncoderEditPlan, keep_factors: bool = False, trace: bool = False,
                      restore: bool = False) -> List[LayerEdit]:
     """Device-only Stage 2 for one encoder.  On return the edited fc2 weights hold W0 + dW (``restore=False``)
@@ -570,214 +651,132 @@ def run_encoder_edit(plan: EncoderEditPlan, keep_factors: bool = False, trace: b
         guard.check(plan.graph.layers, plan.layers[-1] + 1)
     d, h = weights[plan.layers[0]].shape[1], weights[plan.layers[0]].shape[0]
     dev = weights[plan.layers[0]].device
-    dual = _use_dual(plan, d)
+    form = solver_form(plan, d, keep_factors)
     edits: List[LayerEdit] = []
     last = plan.layers[-1]
-    handles = []
-    fac_done = None
-    lazy, first_x = False, 0
+    fac_done, lazy = None, False
     plan.factor_key, plan.factors_from_cache = None, False
-    if dual:
+    if form in DUAL_FORMS:
         plan.dual_ws = _workspace("dual", plan.n_total, d, h, dev, plan)
         plan.dual_ws.info.zero_()
-        fkey = factor_cache_key([plan.covs[l] for l in plan.layers], plan.lam, plan.edit_weight)
-        with ENGINE_LOCK:
-            hit = _FACTOR_CACHE.get(fkey) if _factor_cache_size() > 0 and plan.lam > 0 else None
-            if hit is not None and not (hit[0].lam and hit[0].lam > 0):
-                hit = None
-            if hit is not None:
-                _FACTOR_CACHE.move_to_end(fkey)
-        if hit is not None:
-            # lam0 * C'_l = L L^T and X = inv(L) of every edited layer are already in HBM from an earlier edit with the
-            # same statistics and edit_weight (any lam0: the solve stages take lam / lam0): every M-solve of this pass is a
-            # GEMM against X, nothing is factored but the N x N systems
-            plan.cov_factors, plan.factors_from_cache = hit[0], True
-            if plan.cov_factors.ready is not None:
-                torch.cuda.current_stream(dev).wait_event(plan.cov_factors.ready)
-        else:
-            # lam * C'_l does not depend on the concepts: factor it for ALL edited layers in one batched pass on a side
-            # stream, underneath the encoder forward that produces the first layer's keys
-            if plan.side_stream is None:
-                # high priority: the factorization is a long chain of small dependent kernels; each must get the next
-                # free CU ahead of the forward's wide GEMMs or the chain stretches to several times its own length
-                plan.side_stream = torch.cuda.Stream(device=dev, priority=-1)
-            plan.side_stream.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(plan.side_stream):
-                if plan.cov_factors is not None and plan.cov_factors.cached:
-                    plan.cov_factors = None        # never refactor into a workspace the cache hands to other edits
-                if plan.cov_factors is not None:
-                    plan.cov_factors.info.zero_()
-                plan.cov_factors = hip.factor_cov([plan.covs[l] for l in plan.layers], plan.lam, plan.edit_weight,
-                                                  plan.cov_factors, inverse=False)
-                plan.factor_key = fkey
-                chol_done = torch.cuda.Event()
-                chol_done.record(plan.side_stream)
-                # The first edited layer solves against M by block substitution with L as soon as the factorization is there.
-                # The explicit inverse factors X_l = inv(L_l) of the LATER layers (their two M-solves become two GEMMs) are
-                # built one layer ahead, on the side stream, exactly while the previous layer's solve sits in the
-                # latency-bound Cholesky of its N x N system (the chip is idle there): see ``lazy_inverse`` in solve().
-                # (Building them all right after the factorization, batched underneath the forward, cost the forward more than it
-                # hid: HISTORY.md §5.)
-                first_x = min(L, 1)
-                lazy = keep_factors is False
-                if plan.shard.collective and not keep_factors and -(-d // hip.NB) >= plan.shard.world:
-                    first_x, lazy = 0, False      # the column-sharded solve multiplies by X in every layer
-                fac_done = [chol_done] * L
-                if lazy and first_x == 0:      # the first layer's X right behind the factorization, the others one layer ahead
-                    hip.cov_inverse(plan.cov_factors, 0, 1)
-                    fac_done[0] = torch.cuda.Event()
-                    fac_done[0].record(plan.side_stream)
-                if first_x < L and not lazy:
-                    hip.cov_inverse(plan.cov_factors, first_x, L - first_x)
-                    ev = torch.cuda.Event()
-                    ev.record(plan.side_stream)
-                    for i in range(first_x, L):
-                        fac_done[i] = ev
-            if first_x >= L:
-                lazy = False
-    elif _solver_mode(plan) == "lu":
-        plan.ws = _workspace("lu", plan.n_total, d, h, dev, plan)
-        plan.ws.info.zero_()
-        plan.dual_ws = None
+        fac_done, lazy = _dual_factors(plan, form, dev)
     else:
-        plan.ws = _workspace("direct", plan.n_total, d, h, dev, plan)
+        plan.ws = _workspace("lu" if form == "lu" else "direct", plan.n_total, d, h, dev, plan)
         plan.ws.info.zero_()
+        if form == "lu":
+            plan.dual_ws = None
 
     def solve(i, layer, K_local, Zc_local):
         """All-gather the shard's K/Zc rows, run the closed form, leave W0 + dW in the live weight.  ``Zc_local`` may be
         a callable K -> Zc (fc2 applied to the gathered keys): then only K crosses the links."""
         try:
             with _dist_phase("solve (incl. its collectives)", dev):
-                _solve(i, layer, K_local, Zc_local)
+                K = _all_gather_rows(K_local, plan)
+                Zc = Zc_local(K) if callable(Zc_local) else _all_gather_rows(Zc_local, plan)
+                plan.resolve_targets()
+                if fac_done is not None:
+                    torch.cuda.current_stream(dev).wait_event(fac_done[i])
+                dW, Xt, Rt = _solve(i, layer, K, Zc)
+                edits.append(LayerEdit(layer, plan.weight_name(layer), dW, Xt, Rt, K if trace else None, Zc if trace else None))
         finally:
             _touch(weights[layer])
 
-    def _solve(i, layer, K_local, Zc_local):
-        K = _all_gather_rows(K_local, plan)
-        Zc = Zc_local(K) if callable(Zc_local) else _all_gather_rows(Zc_local, plan)
-        plan.resolve_targets()
-        if dual:
-            if fac_done is not None:
-                torch.cuda.current_stream(dev).wait_event(fac_done[i])
-            sharded = plan.shard.collective
-            if not keep_factors:   # only the edited weights are wanted: the form that never builds adj_k
-                def lazy_inverse(nxt=i + 1):
-                    # stream position: S of layer i is assembled, its Cholesky starts now -> build X of the next layer
-                    start = torch.cuda.Event()
-                    start.record(torch.cuda.current_stream(dev))
-                    plan.side_stream.wait_event(start)
-                    with torch.cuda.stream(plan.side_stream):
-                        hip.cov_inverse(plan.cov_factors, nxt, 1)
-                        fac_done[nxt] = torch.cuda.Event()
-                        fac_done[nxt].record(plan.side_stream)
+    def _solve(i, layer, K, Zc):
+        """The closed form of ``form`` for edited layer ``i``: (dW, adj_k^T | None, resid^T | None)."""
+        W0, W = backups[layer], weights[layer].data
+        if form == "dual_cols":
+            # Every rank holds all N key rows (the K all-gather above).  The layer's GEMMs are split by 128-wide
+            # column tiles of d: a rank forms its columns of Yt = Kt X^T and its share of S = I + Yt Yt^T and of
+            # U = (Z^T Yt) X; S (N x N) and U (h x d) are summed over the ranks (two all-reduces over xGMI), the
+            # N x N Cholesky and the h-row solves are repeated by everyone (latency-bound, no d^2 work in them).
+            res = hip.edit_layer_dual_cols(
+                K, Zc, plan.zs_t, plan.cov_factors, i, plan.edit_weight, L - i, W0, W,
+                hip.column_tiles(plan.shard.rank, plan.shard.world, -(-d // hip.NB)),
+                lambda t: _all_reduce_sum(t, plan.shard.group), ws=plan.dual_ws, lam=plan.lam)
+            return res["dW"], None, None
+        if form == "dual_apply":     # only the edited weights are wanted: the form that never builds adj_k
+            def lazy_inverse(nxt=i + 1):
+                # stream position: S of layer i is assembled, its Cholesky starts now -> build X of the next layer
+                start = torch.cuda.Event()
+                start.record(torch.cuda.current_stream(dev))
+                plan.side_stream.wait_event(start)
+                with torch.cuda.stream(plan.side_stream):
+                    hip.cov_inverse(plan.cov_factors, nxt, 1)
+                    fac_done[nxt] = torch.cuda.Event()
+                    fac_done[nxt].record(plan.side_stream)
 
-                ahead = lazy and max(first_x, 1) <= i + 1 < L
-                if sharded and -(-d // hip.NB) >= plan.shard.world:
-                    # Every rank holds all N key rows (the K all-gather above).  The layer's GEMMs are split by 128-wide
-                    # column tiles of d: a rank forms its columns of Yt = Kt X^T and its share of S = I + Yt Yt^T and of
-                    # U = (Z^T Yt) X; S (N x N) and U (h x d) are summed over the ranks (two all-reduces over xGMI), the
-                    # N x N Cholesky and the h-row solves are repeated by everyone (latency-bound, no d^2 work in them).
-                    n_tiles = -(-d // hip.NB)
-                    res = hip.edit_layer_dual_cols(
-                        K, Zc, plan.zs_t, plan.cov_factors, i, plan.edit_weight, L - i, backups[layer], weights[layer].data,
-                        hip.column_tiles(plan.shard.rank, plan.shard.world, n_tiles),
-                        lambda t: _all_reduce_sum(t, plan.shard.group), ws=plan.dual_ws, lam=solve_lam(plan))
-                    edits.append(LayerEdit(layer, plan.weight_name(layer), res["dW"], None, None,
-                                           K if trace else None, Zc if trace else None))
-                    return
-                # (fewer 128-column tiles than ranks: every rank runs the whole layer itself)
-                split = False
-                res = hip.edit_layer_dual_apply(
-                    K, Zc, plan.zs_t, plan.cov_factors, i, plan.edit_weight, L - i, backups[layer], weights[layer].data,
-                    ws=plan.dual_ws, rows=plan.concept_bounds() if split else None,
-                    gather_yt=(lambda rows_: _all_gather_rows(rows_.contiguous(), plan)) if split else None,
-                    on_factor_start=lazy_inverse if ahead else None, lam=solve_lam(plan))
-                edits.append(LayerEdit(layer, plan.weight_name(layer), res["dW"], None, None,
-                                       K if trace else None, Zc if trace else None))
-                return
+            res = hip.edit_layer_dual_apply(K, Zc, plan.zs_t, plan.cov_factors, i, plan.edit_weight, L - i, W0, W,
+                                            ws=plan.dual_ws, on_factor_start=lazy_inverse if lazy and i + 1 < L else None,
+                                            lam=plan.lam)
+            return res["dW"], None, None
+        if form == "dual":
+            sharded = plan.shard.collective
             res = hip.edit_layer_dual(
-                K, Zc, plan.zs_t, plan.cov_factors, i, plan.edit_weight, L - i, W0=backups[layer], W=weights[layer].data,
-                want_factors=keep_factors, ws=plan.dual_ws,
-                rows=plan.concept_bounds() if sharded else None,
-                gather_pt=(lambda rows_: _all_gather_rows(rows_.contiguous(), plan)) if sharded else None, lam=solve_lam(plan))
-            xt = res["adj_k"].t() if res["adj_k"] is not None else None
-            edits.append(LayerEdit(layer, plan.weight_name(layer), res["dW"], xt, res["Rt"],
-                                   K if trace else None, Zc if trace else None))
-            return
-        if _solver_mode(plan) == "lu":
+                K, Zc, plan.zs_t, plan.cov_factors, i, plan.edit_weight, L - i, W0=W0, W=W, want_factors=keep_factors,
+                ws=plan.dual_ws, rows=plan.concept_bounds() if sharded else None,
+                gather_pt=(lambda rows_: _all_gather_rows(rows_.contiguous(), plan)) if sharded else None, lam=plan.lam)
+            return res["dW"], (res["adj_k"].t() if res["adj_k"] is not None else None), res["Rt"]
+        if form == "lu":
             # the reference's own algorithm (LU with partial pivoting) for a system the Cholesky paths rejected; every
             # rank holds all N key rows here and solves the whole layer itself (rare path, never sharded)
             res = hip.edit_layer_lu(K, Zc, plan.zs_t, plan.covs[layer], plan.lam, plan.edit_weight, L - i,
-                                    W0=backups[layer], W=weights[layer].data, want_factors=keep_factors, ws=plan.ws)
-            xt = res["adj_k"].t() if res["adj_k"] is not None else None
-            edits.append(LayerEdit(layer, plan.weight_name(layer), res["dW"], xt, res["Rt"],
-                                   K if trace else None, Zc if trace else None))
-            return
-        if plan.shard.collective and not keep_factors:
+                                    W0=W0, W=W, want_factors=keep_factors, ws=plan.ws)
+            return res["dW"], (res["adj_k"].t() if res["adj_k"] is not None else None), res["Rt"]
+        if form == "direct_rows":
             # every rank assembles and factors A from all N concepts; the triangular solves and the dW
             # contraction are split by concept rows and the partial U summed over xGMI (fp64, h*d*8 bytes)
             res = hip.edit_layer_shard(K, Zc, plan.zs_t, plan.covs[layer], plan.lam, plan.edit_weight, L - i,
                                        plan.concept_bounds(), ws=plan.ws)
             _all_reduce_sum(res["U"], plan.shard.group)
-            dW = hip.apply_update_(res["U"], backups[layer], weights[layer].data)
-            res = {"dW": dW, "Xt": None, "Rt": None}
-        else:
-            res = hip.edit_layer(K, Zc, plan.zs_t, plan.covs[layer], plan.lam, plan.edit_weight, L - i,
-                                 W0=backups[layer], W=weights[layer].data, want_factors=keep_factors, ws=plan.ws)
-        edits.append(LayerEdit(layer, plan.weight_name(layer), res["dW"], res["Xt"], res["Rt"],
-                               K if trace else None, Zc if trace else None))
+            return hip.apply_update_(res["U"], W0, W), None, None
+        res = hip.edit_layer(K, Zc, plan.zs_t, plan.covs[layer], plan.lam, plan.edit_weight, L - i,
+                             W0=W0, W=W, want_factors=keep_factors, ws=plan.ws)
+        return res["dW"], res["Xt"], res["Rt"]
 
-    if plan.chunks is not None and plan.graph is not None:
-        chunks, order = plan.chunks, {l: i for i, l in enumerate(plan.layers)}
+    if plan.chunk is not None and plan.graph is not None:
+        ch, order = plan.chunk, {l: i for i, l in enumerate(plan.layers)}
         if sorted(plan.layers) != plan.layers:
             raise RuntimeError("hparams.layers must be in forward order")
         first_edit = plan.layers[0]
+        lin = clip_forward.linear
+        # the one-call form of an edited layer: single rank, the apply-only dual solver on factors that are already in HBM
+        # (a warm call), the split-fp16 forward with its native runner
+        fused_run = os.environ.get("EMCID_FUSED_EDIT_LAYER", "1") != "0" and form == "dual_apply" \
+            and not plan.shard.collective and plan.factors_from_cache and clip_forward.NATIVE_RUNNER
 
-        def rows_at(x, idx, ch):   # (rows, c) activations -> per-concept means at the lookup rows of its prompts
+        def keys(li, x):           # this rank's (N_local k, d) key rows: per-concept means at the lookup rows of its prompts
             if isinstance(x, hip.SplitRows):       # split-fp16 path: the keys come from the fp32 twin fc1's epilogue wrote
                 x = x.float()
+            idx = ch.lookup_query if li == last else ch.lookup_node
             return hip.gather_mean(x.unsqueeze(0).expand(idx.numel(), -1, -1), idx, ch.cseg)
 
-        def keys(li, xs):          # this rank's (N_local k, d) key rows, slices concatenated in request order
-            parts = [rows_at(x, ch.lookup_query if li == last else ch.lookup_node, ch) for x, ch in zip(xs, chunks)]
-            return parts[0] if len(parts) == 1 else torch.cat(parts, dim=0)
-
-        zc_from_keys = True      # Zc = fc2(mean keys): fc2 is affine (the other form, fc2 over every node + gather, left in round 5)
-        fused_env = os.environ.get("EMCID_FUSED_EDIT_LAYER", "1") != "0"
-
-        def fused_layer_ok(li, xs, mids):
-            """The one-call form of an edited layer: single rank, one prompt slice, the apply-only dual solver on factors that
-            are already in HBM (a warm call), the split-fp16 forward with its native runner."""
-            if not (fused_env and zc_from_keys and dual and not keep_factors and not plan.shard.collective and mids is not None
-                    and len(chunks) == 1 and plan.factors_from_cache and fac_done is None and clip_forward.NATIVE_RUNNER):
-                return False
-            x = xs[0]
-            if not (isinstance(x, hip.SplitRows) and x.f32 is not None and x.f32.is_contiguous()):
+        def fused_layer_ok(li, x):
+            if not (fused_run and isinstance(x, hip.SplitRows) and x.f32 is not None and x.f32.is_contiguous()):
                 return False
             gl = plan.graph.layers[li]
             if gl.fc2 is not mods[li] or gl.fc2.bias is None:
                 return False
-            return clip_forward.native_of(plan.graph, chunks[0].trie, li, li + 1) is not None
+            return clip_forward.native_of(plan.graph, ch.trie, li, li + 1) is not None
 
-        def on_fc2(li, xs, outs, mids=None, next_ln=None):
-            """fc2 of an edited layer: keys -> closed form -> the projection with the NEW weight.  ``mids`` (the residual
-            streams): the callback returns fc2(x) + mid, the add riding in the GEMM's epilogue; with the native layer runner
-            (hs, LN1 planes of the next layer) pairs from ONE C call (``next_ln``: that LayerNorm, or None)."""
+        def on_fc2(li, x, out, mid=None, next_ln=None):
+            """fc2 of an edited layer: keys -> closed form -> fc2(x) + mid with the NEW weight (the add riding in the GEMM's
+            epilogue); with the native layer runner the (hs, LN1 planes of the next layer) pair from ONE C call (``next_ln``:
+            that LayerNorm, or None)."""
             if li not in order:
-                return outs
+                return out
             m = mods[li]
-            if fused_layer_ok(li, xs, mids):
+            if fused_layer_ok(li, x):
                 # keys, Zc, the solve, the new weight's planes and fc2 + residual + the next LN1: ONE C call
                 # (csrc/clip_layers.hip: emcid_clip_edit_layer_tail_sp16)
-                ch, x, i = chunks[0], xs[0], order[li]
+                i = order[li]
                 nat = clip_forward.native_of(plan.graph, ch.trie, li, li + 1)
                 plan.resolve_targets()
                 w = weights[li]
                 try:
                     res = hip.clip_edit_layer_tail(
-                        nat.array, li, nat.h, nat.d, x, mids[0], ch.lookup_query if li == last else ch.lookup_node,
+                        nat.array, li, nat.h, nat.d, x, mid, ch.lookup_query if li == last else ch.lookup_node,
                         ch.cseg, plan.zs_t, plan.cov_factors, i, plan.edit_weight, L - i, backups[li], w.data, plan.dual_ws,
-                        solve_lam(plan), next_ln, last=li == last)
+                        plan.lam, next_ln, last=li == last)
                 finally:
                     _touch(w)
                 if li != last:      # the layer's fc2 planes were re-split in place from the new weight: keep the cache entry
@@ -788,39 +787,30 @@ def run_encoder_edit(plan: EncoderEditPlan, keep_factors: bool = False, trace: b
                 edits.append(LayerEdit(li, plan.weight_name(li), res["dW"], None, None, res["K"] if trace else None,
                                        res["Zc"] if trace else None))
                 clip_forward.LAST_PATHS["fused_edit_layers"] = clip_forward.LAST_PATHS.get("fused_edit_layers", 0) + 1
-                return None if li == last else [(res["hs"], res["x"])]
-            K_loc = keys(li, xs)
-            lin = clip_forward.linear
-            if not zc_from_keys:
-                solve(order[li], li, K_loc, keys(li, [lin(x, m.weight, m.bias) for x in xs]))
-            else:
-                # fc2 is affine, so the mean over a request's prompts of its output at the lookup rows IS fc2 of the mean
-                # key: Zc = K W^T + b on N rows (to fp32 rounding) instead of fc2 over every node followed by a gather
-                # (on the split-fp16 kernel against the planes of the weight as it is now, like the fused call above)
-                solve(order[li], li, K_loc, lambda K_all: lin(K_all, m.weight, m.bias, wsp=plan.graph.layers[li].split_of("fc2")))
+                return None if li == last else (res["hs"], res["x"])
+            # fc2 is affine, so the mean over a request's prompts of its output at the lookup rows IS fc2 of the mean
+            # key: Zc = K W^T + b on N rows (to fp32 rounding) instead of fc2 over every node followed by a gather
+            # (on the split-fp16 kernel against the planes of the weight as it is now, like the fused call above)
+            solve(order[li], li, keys(li, x), lambda K_all: lin(K_all, m.weight, m.bias, wsp=plan.graph.layers[li].split_of("fc2")))
             if li == last:
                 return None
             wsp = plan.graph.layers[li].split_of("fc2")          # of the NEW weight (solve() bumped its version counter)
-            if mids is not None and wsp is not None and all(isinstance(x, hip.SplitRows) for x in xs):
-                nats = [clip_forward.native_of(plan.graph, ch.trie, li, li + 1) for ch in chunks]
-                if all(n is not None for n in nats):       # fc2 + residual add + the next layer's LN1: one C call per slice
-                    return [hip.clip_layer_tail(n.array, li, n.h, n.d, x, mid, next_ln) for n, x, mid in zip(nats, xs, mids)]
-            if mids is None:
-                return [lin(x, m.weight, m.bias, wsp=wsp) for x in xs]
-            return [lin(x, m.weight, m.bias, residual=mid, wsp=wsp) for x, mid in zip(xs, mids)]
+            if wsp is not None and isinstance(x, hip.SplitRows):
+                nat = clip_forward.native_of(plan.graph, ch.trie, li, li + 1)
+                if nat is not None:        # fc2 + residual add + the next layer's LN1: one C call
+                    return hip.clip_layer_tail(nat.array, li, nat.h, nat.d, x, mid, next_ln)
+            return lin(x, m.weight, m.bias, residual=mid, wsp=wsp)
 
         with torch.no_grad():
             # the unedited leading layers: already launched by prepare (underneath the host's tokenization), else here
-            states = []
-            for ch in chunks:
-                if ch.state is not None and ch.state[0] == first_edit:
-                    states.append((ch.state[1], ch.state[2]))
-                else:
-                    states.append(clip_forward.run_prefix(plan.graph, ch.trie, first_edit))
-                ch.state = None         # single use: the residual stream below belongs to the weights of this very call
+            if ch.state is not None and ch.state[0] == first_edit:
+                state = ch.state[1:]
+            else:
+                state = clip_forward.run_prefix(plan.graph, ch.trie, first_edit)
+            ch.state = None         # single use: the residual stream below belongs to the weights of this very call
             clip_forward.LAST_PATHS["forward_trie"] += 1
-            clip_forward.run_layers_multi(plan.graph, [ch.trie for ch in chunks], states, first_edit, last, on_fc2,
-                                          fc2_by_callback=order, callback_adds_residual=True, split_aware=True)
+            clip_forward.run_layers_from(plan.graph, ch.trie, state, first_edit, last, on_fc2, fc2_by_callback=order,
+                                         edit_callback=True)
     else:
         def make_hook(i, layer):
             def hook(mod, inputs, output):
@@ -833,8 +823,7 @@ def run_encoder_edit(plan: EncoderEditPlan, keep_factors: bool = False, trace: b
             return hook
 
         clip_forward.LAST_PATHS["forward_hf"] += 1
-        for i, l in enumerate(plan.layers):
-            handles.append(mods[l].register_forward_hook(make_hook(i, l)))
+        handles = [mods[l].register_forward_hook(make_hook(i, l)) for i, l in enumerate(plan.layers)]
         try:
             with torch.no_grad(), hip_attention(te):
                 try:
@@ -847,21 +836,9 @@ def run_encoder_edit(plan: EncoderEditPlan, keep_factors: bool = False, trace: b
     if len(edits) != L:
         raise RuntimeError(f"only {len(edits)} of {L} edited layers were reached by the forward pass "
                            f"(hparams.layers must be in forward order)")
-    if dual and plan.factor_key is not None and _factor_cache_size() > 0:
-        # this pass factored lam*C' itself: finish the explicit inverse factors it did not need (off the critical path,
-        # on the side stream) so that check_info can hand the complete set to later edits
-        missing = [i for i in range(L) if i not in plan.cov_factors.have_inverse]
-        if missing:
-            plan.side_stream.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(plan.side_stream):
-                for i in missing:
-                    hip.cov_inverse(plan.cov_factors, i, 1)
-                plan.cov_factors.ready = torch.cuda.Event()
-                plan.cov_factors.ready.record(plan.side_stream)
+    _finish_inverse_factors(plan, dev)
     if restore:
-        with torch.no_grad():
-            for l, w in weights.items():
-                w.copy_(backups[l])
+        plan.restore_weights()
     if guard is not None:
         guard.flush()       # fingerprints of every weight a cache entry was made from in this pass (the edited fc2's as they are NOW)
     return edits
@@ -895,22 +872,29 @@ def solver_info(plan: EncoderEditPlan) -> int:
 
 
 def run_checked(plan: EncoderEditPlan, keep_factors: bool = False, restore: bool = False) -> List[LayerEdit]:
-    """run_encoder_edit + check_info with the reference's fallback semantics: if a Cholesky factorization met a
-    non-positive pivot (lam*C' + K K^T not positive definite, e.g. statistics that lost definiteness in fp32), the
-    weights are put back and the whole pass is rerun with LU + partial pivoting — torch.linalg.solve's algorithm
-    (reference emcid_main.py:1045), which returns numbers for any nonsingular system.  EMCID_LU_FALLBACK=0 raises instead."""
+    """run_encoder_edit + check_info with the reference's fallback semantics (``rerun_with_lu``)."""
     edits = run_encoder_edit(plan, keep_factors=keep_factors, restore=restore)
     try:
         check_info(plan)
-    except FloatingPointError:
-        if os.environ.get("EMCID_LU_FALLBACK", "1") == "0" or plan.solver == "lu":
-            raise
-        plan.solver = "lu"
-        plan.cov_factors = None
-        clip_forward.LAST_PATHS["lu_fallbacks"] = clip_forward.LAST_PATHS.get("lu_fallbacks", 0) + 1
-        logging.getLogger("emcid_amd").warning("a Cholesky factorization met a non-positive pivot: the pass is rerun with the pivoted-LU solver")
-        edits = run_encoder_edit(plan, keep_factors=keep_factors, restore=restore)
-        check_info(plan)
+    except FloatingPointError as err:
+        edits = rerun_with_lu(plan, err, keep_factors=keep_factors, restore=restore)
+    return edits
+
+
+def rerun_with_lu(plan: EncoderEditPlan, err: FloatingPointError, keep_factors: bool = False,
+                  restore: bool = False) -> List[LayerEdit]:
+    """After check_info raised ``err`` (a Cholesky factorization met a non-positive pivot: lam*C' + K K^T not positive
+    definite, e.g. statistics that lost definiteness in fp32; the weights are already back): rerun the whole pass with LU +
+    partial pivoting — torch.linalg.solve's algorithm (reference emcid_main.py:1045), which returns numbers for any
+    nonsingular system — and check it.  EMCID_LU_FALLBACK=0 raises ``err`` instead."""
+    if os.environ.get("EMCID_LU_FALLBACK", "1") == "0" or plan.solver == "lu":
+        raise err
+    plan.solver = "lu"
+    plan.cov_factors = None
+    clip_forward.LAST_PATHS["lu_fallbacks"] = clip_forward.LAST_PATHS.get("lu_fallbacks", 0) + 1
+    logging.getLogger("emcid_amd").warning("a Cholesky factorization met a non-positive pivot: the pass is rerun with the pivoted-LU solver")
+    edits = run_encoder_edit(plan, keep_factors=keep_factors, restore=restore)
+    check_info(plan)
     return edits
 
 
@@ -922,10 +906,7 @@ def check_info(plan: EncoderEditPlan, restore_on_failure: bool = True):
     _release_workspaces(plan)
     if getattr(plan, "stale_weights", False):
         # a weight was rewritten without its version counter moving: this pass ran on planes of the OLD bytes
-        if plan.backups is not None:
-            with torch.no_grad():
-                for l, w0 in plan.backups.items():
-                    get_parameter(plan.text_encoder, plan.weight_name(l)).copy_(w0)
+        plan.restore_weights()
         clip_forward.invalidate_weight_caches(plan.text_encoder)
         plan.factor_key, plan.graph = None, None
         raise clip_forward.StaleWeightCacheError(
@@ -934,10 +915,8 @@ def check_info(plan: EncoderEditPlan, restore_on_failure: bool = True):
             "again (emcid_main's entry points do so by themselves), and bump the counter or call "
             "emcid_amd.invalidate_weight_caches(text_encoder) after such writes")
     if code != 0 and plan.solver == "lu":
-        if restore_on_failure and plan.backups is not None:
-            with torch.no_grad():
-                for l, w0 in plan.backups.items():
-                    get_parameter(plan.text_encoder, plan.weight_name(l)).copy_(w0)
+        if restore_on_failure:
+            plan.restore_weights()
         raise torch.linalg.LinAlgError(
             f"lam*C + K K^T is singular to working precision (zero pivot at column {code - 1} of the pivoted LU): "
             f"torch.linalg.solve (reference emcid_main.py:1045) raises for this system too; the edited weights have been restored")
@@ -953,10 +932,8 @@ def check_info(plan: EncoderEditPlan, restore_on_failure: bool = True):
     if plan.factor_key is not None:
         plan.factor_key = None
         plan.cov_factors = None
-    if restore_on_failure and plan.backups is not None:
-        with torch.no_grad():
-            for l, w0 in plan.backups.items():
-                get_parameter(plan.text_encoder, plan.weight_name(l)).copy_(w0)
+    if restore_on_failure:
+        plan.restore_weights()
     raise FloatingPointError(
         f"lam*C + K K^T is not positive definite (non-positive pivot at column {code - 1}); the reference's LU "
         f"(torch.linalg.solve, emcid_main.py:1045) returns numbers for an indefinite system — the edited weights have been "

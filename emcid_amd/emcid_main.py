@@ -33,7 +33,7 @@ import torch
 
 from . import clip_forward, edit_engine, hip, nethook
 from .edit_engine import (ConceptShard, EncoderEditPlan, LayerEdit, check_info, phase, prepare_encoder_edit,
-                          run_checked, run_encoder_edit)
+                          rerun_with_lu, run_checked, run_encoder_edit)
 from .emcid_hparams import EMCIDHyperParams, EMCIDXLHyperParams
 from .globals import STATS_DIR, XL_STATS_DIR1, XL_STATS_DIR2
 from .compute_ks import get_layers_input_output_at_words_cross_attn
@@ -944,9 +944,7 @@ def apply_emcid_to_sdxl_text_encoders(pipe, requests: List[Dict], hparams: EMCID
         # one group's stale caches must not leave the other group waiting in the broadcasts below: every rank learns of it
         if _any_rank(stale is not None, next(pipe.text_encoder.parameters()).device):
             if stale is None:      # the sound group's encoder is edited (TE2 sits at W + 2 dW): put it back before everybody raises
-                with torch.no_grad():
-                    for l, w0 in (plan.backups or {}).items():
-                        nethook.get_parameter(plan.text_encoder, plan.weight_name(l)).copy_(w0)
+                plan.restore_weights()
             raise stale if stale is not None else clip_forward.StaleWeightCacheError(
                 "the other encoder's rank group ran on stale weight caches; this group's weights were restored")
         names = []
@@ -984,26 +982,17 @@ def apply_emcid_to_sdxl_text_encoders(pipe, requests: List[Dict], hparams: EMCID
     stale = None
     for plan, redo in ((p1, None), (p2, double_apply if SDXL_TE2_DOUBLE_APPLY else None)):
         try:
-            check_info(plan)                       # restores the encoder's weights if a factorization failed
+            try:
+                check_info(plan)                   # restores the encoder's weights if a factorization failed
+            except FloatingPointError as err:
+                again = rerun_with_lu(plan, err)   # the reference's own solver semantics, as run_checked
+                if redo is not None:
+                    redo(again)
         except clip_forward.StaleWeightCacheError as e:
             stale = e                              # (this encoder's weights are back; the other one's follow below)
-        except FloatingPointError:
-            if os.environ.get("EMCID_LU_FALLBACK", "1") == "0":
-                raise
-            plan.solver, plan.cov_factors = "lu", None          # the reference's own solver semantics (edit_engine.run_checked)
-            again = run_encoder_edit(plan, keep_factors=False, restore=False)
-            try:
-                check_info(plan)
-            except clip_forward.StaleWeightCacheError as e:     # (weights back; the other encoder's follow below)
-                stale = e
-                continue
-            if redo is not None:
-                redo(again)
     if stale is not None:      # one encoder ran on stale planes: put BOTH back (TE2 sits at W + 2 dW) and let the call be redone
-        with torch.no_grad():
-            for plan in (p1, p2):
-                for l, w0 in (plan.backups or {}).items():
-                    nethook.get_parameter(plan.text_encoder, plan.weight_name(l)).copy_(w0)
+        p1.restore_weights()
+        p2.restore_weights()
         raise stale
     if verbose:
         print(f"New weights successfully inserted into {[e.weight_name for e in e1 + e2]}")

@@ -260,11 +260,13 @@ def edit_workspace_bytes(N: int, d: int, h: int) -> int:
 
 
 class EditWorkspace:
-    """Reusable HBM workspace (+ the device `info` word) for emcid_edit_layer_f64."""
+    """Reusable HBM workspace (+ the device `info` word) of emcid_edit_layer_f64 / emcid_edit_layer_shard_f64, or with ``lu``
+    of the pivoted-LU fallback emcid_edit_layer_lu_f64."""
 
-    def __init__(self, N: int, d: int, h: int, device):
+    def __init__(self, N: int, d: int, h: int, device, lu: bool = False):
         self.key = (N, d, h)
-        self.nbytes = edit_workspace_bytes(N, d, h)
+        self.lu = lu
+        self.nbytes = int(load().emcid_edit_lu_workspace_bytes(N, d, h)) if lu else edit_workspace_bytes(N, d, h)
         self.buf = torch.zeros(self.nbytes // 8, dtype=torch.float64, device=device)      # (zero: padding the stages never write)
         self.info = torch.zeros(1, dtype=torch.int32, device=device)
 
@@ -277,7 +279,7 @@ def edit_layer(K, Zc, zs_t, Cov, lam: float, edit_weight: float, layers_left: in
     assert Cov.shape == (d, d) and zs_t.shape == (N, h) and Zc.shape == (N, h)
     for t, nm in ((K, "K"), (Zc, "Zc"), (zs_t, "zs_t"), (Cov, "C")):
         assert t.is_contiguous(), nm
-    if ws is None or ws.key != (N, d, h):
+    if ws is None or ws.key != (N, d, h) or ws.lu:
         ws = EditWorkspace(N, d, h, K.device)
     dev = K.device
     Xt = torch.empty(N, d, dtype=torch.float64, device=dev) if want_factors else None
@@ -293,18 +295,8 @@ def edit_layer(K, Zc, zs_t, Cov, lam: float, edit_weight: float, layers_left: in
     return {"Xt": Xt, "Rt": Rt, "dW": dW, "ws": ws}
 
 
-class LuWorkspace:
-    """Workspace of the pivoted-LU fallback (emcid_edit_layer_lu_f64)."""
-
-    def __init__(self, N: int, d: int, h: int, device):
-        self.key = (N, d, h)
-        self.nbytes = int(load().emcid_edit_lu_workspace_bytes(N, d, h))
-        self.buf = torch.zeros(self.nbytes // 8, dtype=torch.float64, device=device)      # (zero: padding the stages never write)
-        self.info = torch.zeros(1, dtype=torch.int32, device=device)
-
-
 def edit_layer_lu(K, Zc, zs_t, Cov, lam: float, edit_weight: float, layers_left: int, W0=None, W=None,
-                  want_factors: bool = False, want_dw: bool = True, ws: Optional[LuWorkspace] = None):
+                  want_factors: bool = False, want_dw: bool = True, ws: Optional[EditWorkspace] = None):
     """One edited layer solved like the reference does (LU with partial pivoting, torch.linalg.solve's algorithm): works for
     any nonsingular lam*C' + K K^T.  Returns dict(adj_k (d, N) | None, Rt (N, h) | None, dW, ws)."""
     N, d = K.shape
@@ -312,8 +304,8 @@ def edit_layer_lu(K, Zc, zs_t, Cov, lam: float, edit_weight: float, layers_left:
     assert Cov.shape == (d, d) and zs_t.shape == (N, h) and Zc.shape == (N, h)
     for t, nm in ((K, "K"), (Zc, "Zc"), (zs_t, "zs_t"), (Cov, "C")):
         assert t.is_contiguous(), nm
-    if ws is None or ws.key != (N, d, h):
-        ws = LuWorkspace(N, d, h, K.device)
+    if ws is None or ws.key != (N, d, h) or not ws.lu:
+        ws = EditWorkspace(N, d, h, K.device, lu=True)
     dev = K.device
     adj_k = torch.empty(d, N, dtype=torch.float64, device=dev) if want_factors else None
     Rt = torch.empty(N, h, dtype=torch.float64, device=dev) if want_factors else None
@@ -349,7 +341,7 @@ def edit_layer_shard(K, Zc, zs_t, Cov, lam: float, edit_weight: float, layers_le
     assert Cov.shape == (d, d) and zs_t.shape == (N, h) and Zc.shape == (N, h) and 0 <= lo < hi <= N
     for t, nm in ((K, "K"), (Zc, "Zc"), (zs_t, "zs_t"), (Cov, "C")):
         assert t.is_contiguous(), nm
-    if ws is None or ws.key != (N, d, h):
+    if ws is None or ws.key != (N, d, h) or ws.lu:
         ws = EditWorkspace(N, d, h, K.device)
     dev = K.device
     U = torch.empty(h, d, dtype=torch.float64, device=dev)
@@ -1058,9 +1050,6 @@ class DualWorkspace:
         pt = load().emcid_edit_dual_pt(_ptr(self.buf), N, d, h)
         off = (pt - self.buf.data_ptr()) // 8
         self.Pt = self.buf[off:off + self.Np * self.dp].view(self.Np, self.dp)   # the Pt stack, rows = concepts
-        yt = load().emcid_edit_dual_yt(_ptr(self.buf), N, d, h)
-        off = (yt - self.buf.data_ptr()) // 8
-        self.Yt = self.buf[off:off + self.Np * self.dp].view(self.Np, self.dp)   # the Yt stack of the apply-only form
         hp = h + (h % 2)
         off = (load().emcid_edit_dual_s(_ptr(self.buf), N, d, h) - self.buf.data_ptr()) // 8
         self.S = self.buf[off:off + self.Np * self.Np].view(self.Np, self.Np)    # N x N system (column-sharded form: partial sums)
@@ -1184,7 +1173,7 @@ def edit_layer_dual_cols(K, Zc, zs_t, factors, layer_index: int, edit_weight: fl
 
 
 def edit_layer_dual_apply(K, Zc, zs_t, factors: CovFactors, layer_index: int, edit_weight: float, layers_left: int,
-                          W0, W, want_dw: bool = True, ws: Optional[DualWorkspace] = None, rows=None, gather_yt=None,
+                          W0, W, want_dw: bool = True, ws: Optional[DualWorkspace] = None,
                           use_inverse: Optional[bool] = None, on_factor_start=None, lam: Optional[float] = None):
     """Apply-only dual solver: W = W0 + float(U) without ever forming adj_k.  ``on_factor_start()``: called (host side)
     right after S = I + Yt Yt^T has been enqueued, i.e. the stream position where the latency-bound Cholesky of S
@@ -1198,14 +1187,11 @@ def edit_layer_dual_apply(K, Zc, zs_t, factors: CovFactors, layer_index: int, ed
     assert zs_t.shape == (N, h) and factors.d == d and W.shape == (h, d)
     if ws is None or ws.key != (N, d, h):
         ws = DualWorkspace(N, d, h, K.device)
-    lo, hi = rows if rows is not None else (0, N)
     lib = load()
     _check(lib.emcid_edit_dual_apply_stage1_f64(
         _ptr(K, torch.float32, "K"), _ptr(Zc, torch.float32, "Zc"), _ptr(zs_t, torch.float32, "zs_t"), N, d, h,
-        float(edit_weight), int(layers_left), factors.lam_ratio(lam), _ptr(factors.buf), factors.n_layers, int(layer_index), lo, hi,
+        float(edit_weight), int(layers_left), factors.lam_ratio(lam), _ptr(factors.buf), factors.n_layers, int(layer_index), 0, N,
         int(bool(use_inverse)), _ptr(ws.buf), ws.nbytes, _stream(K)), "emcid_edit_dual_apply_stage1_f64")
-    if gather_yt is not None:
-        ws.Yt[:N].copy_(gather_yt(ws.Yt[lo:hi]))
     dW = torch.empty(h, d, dtype=torch.float32, device=K.device) if want_dw else None
     if on_factor_start is not None:
         _check(lib.emcid_edit_dual_apply_assemble_f64(N, d, h, _ptr(ws.buf), ws.nbytes, _stream(K)),

@@ -50,8 +50,8 @@ for reqs in sets:
     t = lap("last_tokens (native walk)", t)
     chunk_ids = np.ascontiguousarray(ids[:, :int(lk.max()) + 1])
     t = lap("truncate + contiguous", t)
-    whole = next(cz.iter_prompt_chunks(tok, reqs, 1, defer_probe=True))
-    t = lap("iter_prompt_chunks as a whole (deferred probe)", t)
+    whole = cz.prompt_chunk(tok, reqs, defer_probe=True)
+    t = lap("prompt_chunk as a whole (deferred probe)", t)
     whole.verify()
     t = lap("the deferred probe itself", t)
     trie = clip_forward.build_trie(whole.ids, whole.lookup, dev, tail=np.cumsum([0] + list(whole.counts)).astype(np.int64))

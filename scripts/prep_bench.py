@@ -12,9 +12,8 @@ sets=[syn.make_requests(1000,names="syllable",name_seed=3+101*i) for i in range(
 i=[0]
 def prep():
     reqs=sets[i[0]%60]; i[0]+=1
-    it=cz.iter_prompt_chunks(tok, reqs, 1, defer_probe=True)
-    return next(it)
-m,mn,pc=bench(prep); print("iter_prompt_chunks median %.3f min %.3f ms"%(m,mn), "TOK_THREADS", os.environ.get("EMCID_TOK_THREADS"), pc.ids.shape)
+    return cz.prompt_chunk(tok, reqs, defer_probe=True)
+m,mn,pc=bench(prep); print("prompt_chunk median %.3f min %.3f ms"%(m,mn), "TOK_THREADS", os.environ.get("EMCID_TOK_THREADS"), pc.ids.shape)
 def trie():
     return cf.build_trie(pc.ids, pc.lookup, "cpu", tail=np.cumsum([0]+list(pc.counts)).astype(np.int64))
 m,mn,t=bench(trie); print("build_trie median %.3f min %.3f ms"%(m,mn), t.n_nodes)

@@ -695,7 +695,7 @@ def test_templated_path_deferred_probe(monkeypatch):
     assert host_text.NativeClipBpe.for_tokenizer(tok) is not None
     assert np.asarray(sure.lookup).tolist()[0] < np.asarray(early.lookup).tolist()[0]
     monkeypatch.setenv("EMCID_TEMPLATED", "0")
-    _chunks_equal(sure, list(cz.iter_prompt_chunks(tok, twice, 1))[0])
+    _chunks_equal(sure, cz.prompt_chunk(tok, twice))
     monkeypatch.setenv("EMCID_TEMPLATED", "1")
     third = cz.templated_prompt_chunk(tok, syn.make_requests(40, names="syllable", name_seed=79), reqs[0], defer_probe=True)
     real = type(tok).__call__
@@ -709,9 +709,9 @@ def test_templated_path_deferred_probe(monkeypatch):
     assert third.verify() is False
     monkeypatch.setattr(type(tok), "__call__", real)
     assert host_text.NativeClipBpe.for_tokenizer(tok) is None and cz.templated_prompt_chunk(tok, reqs, reqs[0]) is None
-    chunks = list(cz.iter_prompt_chunks(tok, reqs, 1, defer_probe=True))          # generic path now: nothing left to verify
-    assert len(chunks) == 1 and chunks[0].verify is None
-    _chunks_equal(chunks[0], now)
+    chunk = cz.prompt_chunk(tok, reqs, defer_probe=True)          # generic path now: nothing left to verify
+    assert chunk.verify is None
+    _chunks_equal(chunk, now)
 
 
 def test_templated_prompt_path_equals_generic_path(monkeypatch):
@@ -726,20 +726,16 @@ def test_templated_prompt_path_equals_generic_path(monkeypatch):
     if host_text.NativeClipBpe.for_tokenizer(tok) is None:
         pytest.skip("no native twin for the synthetic tokenizer")
 
-    def both(reqs, n_chunks=1):
+    def both(reqs):
         monkeypatch.setenv("EMCID_TEMPLATED", "1")
-        fast = list(cz.iter_prompt_chunks(tok, reqs, n_chunks))
+        fast = cz.prompt_chunk(tok, reqs)
         monkeypatch.setenv("EMCID_TEMPLATED", "0")
-        slow = list(cz.iter_prompt_chunks(tok, reqs, n_chunks))
-        assert len(fast) == len(slow)
-        for a, b in zip(fast, slow):
-            _chunks_equal(a, b)
+        _chunks_equal(fast, cz.prompt_chunk(tok, reqs))
         return fast
 
     reqs = syn.make_requests(300, names="syllable")
     assert cz.templated_prompt_chunk(tok, reqs, reqs[0]) is not None        # the fast path really serves the bench shape
     both(reqs)
-    both(reqs, n_chunks=3)
     both(syn.make_requests(4500, names="syllable", name_seed=5))      # >= 4 096 names: the threaded name encoding of libemcid_host
     names = syn.syllable_names(12)
     odd = []
@@ -756,7 +752,7 @@ def test_templated_prompt_path_equals_generic_path(monkeypatch):
     for flag in ("1", "0"):
         monkeypatch.setenv("EMCID_TEMPLATED", flag)
         with pytest.raises(ValueError, match="not found in tokens"):
-            list(cz.iter_prompt_chunks(tok, uni, 1))
+            cz.prompt_chunk(tok, uni)
     # outside the templated shape: the generic path must serve these (and the fast one must decline)
     for bad in ([{"source": "ka", "dest": "x", "prompts": ["{0} art", "by {}"], "seed_train": 1}] * 4,
                 [{"source": "ka", "dest": "x", "prompts": ["{{}} {}"], "seed_train": 1}] * 4,
@@ -765,7 +761,7 @@ def test_templated_prompt_path_equals_generic_path(monkeypatch):
         both(bad)
     with pytest.raises(ValueError):                              # subject not in the prompt: the scalar walk's error
         monkeypatch.setenv("EMCID_TEMPLATED", "1")
-        list(cz.iter_prompt_chunks(tok, [{"source": "zu", "dest": "x", "prompts": ["art by ka {}"[:9]], "seed_train": 1}] * 4, 1))
+        cz.prompt_chunk(tok, [{"source": "zu", "dest": "x", "prompts": ["art by ka {}"[:9]], "seed_train": 1}] * 4)
 
 
 def test_templated_prompt_path_randomised(monkeypatch):
@@ -805,15 +801,14 @@ def test_templated_prompt_path_randomised(monkeypatch):
         for flag in ("1", "0"):
             monkeypatch.setenv("EMCID_TEMPLATED", flag)
             try:
-                out[flag] = list(cz.iter_prompt_chunks(tok, reqs, 1))
+                out[flag] = cz.prompt_chunk(tok, reqs)
             except ValueError as e:
                 out[flag] = ("ValueError", str(e)[:40])
         if isinstance(out["0"], tuple) or isinstance(out["1"], tuple):
             assert isinstance(out["0"], tuple) and isinstance(out["1"], tuple), (trial, out["0"] if isinstance(out["0"], tuple) else out["1"])
             continue
         served += cz.templated_prompt_chunk(tok, reqs, reqs[0]) is not None
-        for a, b in zip(out["1"], out["0"]):
-            _chunks_equal(a, b)
+        _chunks_equal(out["1"], out["0"])
     assert served >= 15
 
 

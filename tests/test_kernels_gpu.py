@@ -547,12 +547,12 @@ def test_ill_conditioned_statistics(decades, form):
 
 @pytest.mark.parametrize("decades", [2, 4, 6, 8])
 def test_edit_weight_as_a_scalar_on_ill_conditioned_statistics(decades):
-    """EMCID_EDIT_WEIGHT_SCALAR=1 (edit_engine.solve_lam): factors built for edit_weight 0.5 serve an edit at 0.7 through
-    lam_eff = lam (1 - 0.7)/(1 - 0.5).  Against the oracle's exact form at 0.7 (C' = fl32(fl32(0.3 C)/0.5), reference
-    emcid_main.py:1037) the weights differ by the effect of one fp32 rounding per entry of C', amplified by the condition of
-    the statistics: 3e-7 at cond 1e2, 1e-5 at 1e4 — inside BASELINE.json's 1e-4 — and 6e-4 at 1e6, 5e-2 at 1e8: OUTSIDE it.  That is why the
-    switch is off by default and the exact form refactors; the bound asserted here is the measured
-    envelope 1e-6 + 2e-9 * cond."""
+    """edit_weight treated as a scalar on C (factors built for edit_weight 0.5 serving an edit at 0.7 through
+    lam_eff = lam (1 - 0.7)/(1 - 0.5), handed to the apply-only kernel's ``lam``).  Against the oracle's exact form at 0.7
+    (C' = fl32(fl32(0.3 C)/0.5), reference emcid_main.py:1037) the weights differ by the effect of one fp32 rounding per entry
+    of C', amplified by the condition of the statistics: 3e-7 at cond 1e2, 1e-5 at 1e4 — inside BASELINE.json's 1e-4 — and
+    6e-4 at 1e6, 5e-2 at 1e8: OUTSIDE it.  That is why the engine keys its cached factors by edit_weight and refactors for
+    another one; the bound asserted here is the measured envelope 1e-6 + 2e-9 * cond."""
     N, d, h, lam, ew0, ew = 200, 3072, 768, 4000.0, 0.5, 0.7
     g = torch.Generator().manual_seed(decades)
     Q, _ = torch.linalg.qr(torch.randn(d, d, dtype=torch.float64, generator=g))

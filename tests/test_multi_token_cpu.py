@@ -164,10 +164,9 @@ def test_templated_path_equals_generic_path_multi_token(monkeypatch, k):
     for reqs in (syn.make_requests(300, names="syllable"), syn.make_requests(40, ragged=True, names="syllable")):
         assert cz.templated_prompt_chunk(tok, reqs, reqs[0], num_edit_tokens=k) is not None
         monkeypatch.setenv("EMCID_TEMPLATED", "1")
-        fast = list(cz.iter_prompt_chunks(tok, reqs, 1, num_edit_tokens=k))
+        a = cz.prompt_chunk(tok, reqs, num_edit_tokens=k)
         monkeypatch.setenv("EMCID_TEMPLATED", "0")
-        slow = list(cz.iter_prompt_chunks(tok, reqs, 1, num_edit_tokens=k))
-        (a,), (b,) = fast, slow
+        b = cz.prompt_chunk(tok, reqs, num_edit_tokens=k)
         ia, la, ca, ea = _chunk_arrays(a)
         ib, lb, cb, eb = _chunk_arrays(b)
         assert la.shape == lb.shape == (ia.shape[0], k) and list(ca) == list(cb)
