@@ -1948,6 +1948,68 @@ int emcid_cov_inverse_f64(void* cov_factor_ws, int64_t n_layers, int64_t d, int6
     });
 }
 
+/* ---- a factored workspace at another scale: chol(a M) = sqrt(a) chol(M) ---------------------------------------------------
+ * One launch over the three factor regions of every layer: the NB x NB tiles of L on and below the diagonal times sqrt(a), the
+ * same tiles of X = inv(L) and the whole block of diagonal-block inverses times 1/sqrt(a).  (A diagonal tile is copied whole:
+ * whatever the factorization left above the diagonal inside it travels along, scaled.)  Nothing above the block diagonal is
+ * read or written, and the consumed M region is left alone.  Every access is a double2 (128 bits): dp is a multiple of 128 and
+ * every region starts on an even number of doubles from the 16-byte aligned base.  src == dst scales in place. */
+__global__ __launch_bounds__(256) void cov_factor_rescale_kernel(const double* src, double* dst, int64_t off_L, int64_t off_I,
+                                                                 int64_t off_X, int64_t s_mat, int64_t s_inv, int dp, int n_tri,
+                                                                 double gain_L, double gain_inv, int with_inverse) {
+    const int64_t layer = blockIdx.y;
+    const int region = blockIdx.z;            // 0: L, 1: the diagonal-block inverses, 2: X
+    if (region == 1) {
+        const double2* s = reinterpret_cast<const double2*>(src + off_I + layer * s_inv);
+        double2* o = reinterpret_cast<double2*>(dst + off_I + layer * s_inv);
+        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < s_inv / 2; i += (int64_t)gridDim.x * 256) {
+            double2 v = s[i];
+            v.x *= gain_inv;
+            v.y *= gain_inv;
+            o[i] = v;
+        }
+        return;
+    }
+    if (region == 2 && !with_inverse) return;
+    const int t = blockIdx.x;                 // tile (I, J), J <= I, of the block lower triangle: t = I (I + 1) / 2 + J
+    if (t >= n_tri) return;
+    int I = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
+    while ((I + 1) * (I + 2) / 2 <= t) ++I;
+    while (I * (I + 1) / 2 > t) --I;
+    const int J = t - I * (I + 1) / 2;
+    const int64_t base = (region == 0 ? off_L : off_X) + layer * s_mat + (int64_t)I * NB * dp + (int64_t)J * NB;
+    const double g = region == 0 ? gain_L : gain_inv;
+    // 128 rows of 64 double2: a wavefront covers one row's 1 KiB
+    for (int e = threadIdx.x; e < NB * (NB / 2); e += 256) {
+        const int r = e / (NB / 2), c2 = e % (NB / 2);
+        const int64_t at = base + (int64_t)r * dp + 2 * c2;
+        double2 v = *reinterpret_cast<const double2*>(src + at);
+        v.x *= g;
+        v.y *= g;
+        *reinterpret_cast<double2*>(dst + at) = v;
+    }
+}
+
+int emcid_cov_factor_rescale_f64(const void* src_ws, void* dst_ws, int64_t workspace_bytes, int64_t n_layers, int64_t d, double a,
+                                 int with_inverse, void* stream) {
+    EMCID_CHECK_ARG(src_ws && dst_ws && n_layers > 0 && n_layers <= 32 && d > 0 && d <= 32768);
+    EMCID_CHECK_ARG(aligned16(src_ws) && aligned16(dst_ws) && a > 0.0 && a < 1e300);
+    if (workspace_bytes < emcid_cov_factor_workspace_bytes(n_layers, d))
+        return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small (see emcid_cov_factor_workspace_bytes)");
+    const int64_t dp = round_up(d, NB), s_mat = dp * dp, s_inv = inv_doubles(dp), nt = dp / NB;
+    EMCID_CHECK_ARG(s_inv % 2 == 0);
+    const int n_tri = (int)(nt * (nt + 1) / 2);
+    const double root = sqrt(a);
+    // grid: x = the tiles of the block lower triangle, y = layer, z = region.  Regions 0 and 2 take one tile per workgroup (all of
+    // region 2 leave at once without with_inverse); region 1, the small block of diagonal-block inverses, walks its s_inv / 2
+    // double2 with the same n_tri workgroups as a grid-stride loop: one launch for the three regions.
+    hipLaunchKernelGGL(cov_factor_rescale_kernel, dim3((unsigned)n_tri, (unsigned)n_layers, 3), dim3(256), 0, (hipStream_t)stream,
+                       (const double*)src_ws, (double*)dst_ws, n_layers * s_mat, 2 * n_layers * s_mat, n_layers * (2 * s_mat + s_inv),
+                       s_mat, s_inv, (int)dp, n_tri, root, 1.0 / root, with_inverse);
+    EMCID_CHECK_LAUNCH();
+    return EMCID_OK;
+}
+
 int64_t emcid_edit_dual_workspace_bytes(int64_t N, int64_t d, int64_t h) {
     if (N <= 0 || d <= 0 || h <= 0) return 0;
     return DualWorkspace(N, d, h).total * (int64_t)sizeof(double);

@@ -140,6 +140,7 @@ class EncoderEditPlan:
     factor_key: Optional[tuple] = None   # set by a run that factored lam*C' itself: check_info caches the factors if sound
     factors_from_cache: bool = False
     num_edit_tokens: int = 1             # k > 1: k key / value rows per request (last subject token, EOS, padding), n_total = N k
+    sweep_factors: Optional[hip.CovFactors] = None       # set by run_sweep: the point's rescaled factors, used as they are
 
     def weight_name(self, layer):
         return f"{self.rewrite_module_tmp.format(layer)}.weight"
@@ -566,6 +567,10 @@ def _dual_factors(plan: EncoderEditPlan, form: str, dev):
     turn a layer's two M-solves into two GEMMs.  Returns (fac_done, lazy): per edited layer the event its solve waits for
     (None: the factors came from the cache, nothing to wait for), and whether the solve of layer i builds X of layer i + 1."""
     L = len(plan.layers)
+    if plan.sweep_factors is not None:
+        # a point of run_sweep: the unit-scale factors of the sweep, rescaled to this point's lam and edit_weight, inverses included
+        plan.cov_factors, plan.factors_from_cache = plan.sweep_factors, True
+        return None, False
     fkey = factor_cache_key([plan.covs[l] for l in plan.layers], plan.lam, plan.edit_weight)
     with ENGINE_LOCK:
         hit = _FACTOR_CACHE.get(fkey) if _factor_cache_size() > 0 and plan.lam > 0 else None
@@ -842,6 +847,125 @@ def run_encoder_edit(plan: EncoderEditPlan, keep_factors: bool = False, trace: b
     if guard is not None:
         guard.flush()       # fingerprints of every weight a cache entry was made from in this pass (the edited fc2's as they are NOW)
     return edits
+
+
+# ---- many (mom2_update_weight, edit_weight) pairs over one prepared plan ------------------------------------------------------------
+# The system of a pair is A = a C + b K K^T with a = 2 lam (1 - e), b = 2 e (reference emcid_main.py:1030-1050: C (1 - e) / 0.5, keys
+# and residuals times sqrt(e / 0.5)).  Nothing of the preparation depends on the pair, nor does chol(C): chol(a C) = sqrt(a) chol(C).
+
+def sweep_factor_cache_key(covs: Sequence[torch.Tensor]) -> tuple:
+    """The key of a sweep's unit-scale factors chol(C_l), inv(chol(C_l)) in the factor cache: the statistics alone — neither lam nor
+    edit_weight (``factor_cache_key`` keeps edit_weight: a single call factors the fp32-rounded C' of the reference)."""
+    return ("sweep", tuple((c.device.index, c.data_ptr(), c._version, tuple(c.shape)) for c in covs))
+
+
+def validate_grid(grid) -> List[tuple]:
+    """``grid`` as a list of (mom2_update_weight, edit_weight) float pairs, or ValueError: empty, not pairs, mom2_update_weight <= 0
+    or not finite, edit_weight outside (0, 1) (e = 1 makes a = 0: no Cholesky factor to rescale; e = 0 edits nothing)."""
+    try:
+        pts = [(float(p[0]), float(p[1])) for p in grid] if all(len(p) == 2 for p in grid) else None
+    except (TypeError, ValueError, IndexError) as e:
+        raise ValueError(f"grid must be a sequence of (mom2_weight, edit_weight) pairs: {e}") from e
+    if pts is None:
+        raise ValueError("grid must be a sequence of (mom2_weight, edit_weight) pairs")
+    if not pts:
+        raise ValueError("grid is empty")
+    for lam, e in pts:
+        if not (np.isfinite(lam) and lam > 0.0):
+            raise ValueError(f"mom2_weight must be positive and finite in a sweep (got {lam})")
+        if not (0.0 < e < 1.0):
+            raise ValueError(f"edit_weight must lie inside (0, 1) in a sweep (got {e})")
+    return pts
+
+
+def _sweep_unit_factors(plan: EncoderEditPlan, dev) -> Optional[hip.CovFactors]:
+    """chol(C_l) and its explicit inverse for every edited layer, from the factor cache or factored here (lam = 1, edit_weight = 0.5:
+    C' = fl32(fl32(C 0.5) / 0.5) = C exactly), checked with one host synchronisation per sweep.  None: C is not positive definite."""
+    covs = [plan.covs[l] for l in plan.layers]
+    key = sweep_factor_cache_key(covs)
+    with ENGINE_LOCK:
+        hit = _FACTOR_CACHE.get(key) if _factor_cache_size() > 0 else None
+        if hit is not None:
+            _FACTOR_CACHE.move_to_end(key)
+    if hit is not None:
+        if hit[0].ready is not None:
+            torch.cuda.current_stream(dev).wait_event(hit[0].ready)
+        return hit[0]
+    unit = hip.factor_cov(covs, 1.0, 0.5, None, inverse=True)
+    clip_forward.LAST_PATHS["sweep_cov_factorizations"] += len(covs)
+    if int(unit.info.item()) != 0:
+        return None
+    if _factor_cache_size() > 0:
+        with ENGINE_LOCK:
+            unit.cached = True
+            _FACTOR_CACHE[key] = (unit, covs)
+            while len(_FACTOR_CACHE) > _factor_cache_size():
+                _FACTOR_CACHE.popitem(last=False)
+    return unit
+
+
+def run_sweep(plan: EncoderEditPlan, grid, visit=None) -> list:
+    """Stage 2 of ONE prepared plan at every (mom2_update_weight, edit_weight) pair of ``grid``, in order.  While a point's edited
+    weights are in place ``visit(index, (lam, e))`` is called; its return values are the result.  The weights are back at their
+    original values between the points and on return (also when ``visit`` raises).
+
+    Shared by the points: the plan (tokenization, trie, v* rows), the residual stream entering the first edited layer (the prefix
+    launched by prepare, replayed: run_layers_from only reads it), the choice of the solver, and one factorization of the statistics
+    at unit scale — a point rescales it into its own workspace (hip.cov_factor_rescale) and then runs the chain of a single call on
+    warm factors: run_layers_from, the fused edit-layer call, check_info, rerun_with_lu for a point whose Cholesky reports a pivot
+    (that point only).  LAST_PATHS gauges of the last sweep: sweep_points, sweep_cov_factorizations (len(layers) for a dual form
+    on a cold cache, 0 on cached unit factors or for the direct form, which assembles A from C itself), sweep_prefix_runs (1)."""
+    pts = validate_grid(grid)
+    if plan.chunk is None or plan.graph is None:
+        raise clip_forward.UnsupportedEncoder("run_sweep replays the prefix-trie forward's state")
+    LP = clip_forward.LAST_PATHS
+    LP["sweep_points"] = LP["sweep_cov_factorizations"] = LP["sweep_prefix_runs"] = 0
+    ch, first_edit = plan.chunk, plan.layers[0]
+    w0 = get_parameter(plan.text_encoder, plan.weight_name(first_edit))
+    dev, d = w0.device, w0.shape[1]
+    saved = (plan.lam, plan.edit_weight, plan.solver)
+    results = []
+    try:
+        with phase("sweep: shared"), torch.no_grad():
+            form = solver_form(plan, d, False)          # once: N, d and the shard decide, not the pair
+            pinned = "dual" if form in DUAL_FORMS else form if form == "lu" else "direct"
+            state = ch.state if ch.state is not None and ch.state[0] == first_edit else \
+                (first_edit,) + tuple(clip_forward.run_prefix(plan.graph, ch.trie, first_edit))
+            LP["sweep_prefix_runs"] += 1
+            unit = _sweep_unit_factors(plan, dev) if form in DUAL_FORMS else None
+            if form in DUAL_FORMS and unit is None:
+                # C itself has a non-positive pivot: so has a C for every pair.  Every point is a single call's fallback.
+                logging.getLogger("emcid_amd").warning("the statistics are not positive definite: every point of the sweep runs "
+                                                       "on the pivoted-LU solver")
+                if os.environ.get("EMCID_LU_FALLBACK", "1") == "0":
+                    raise FloatingPointError("the statistics are not positive definite (non-positive pivot in chol(C))")
+                pinned = "lu"
+        scaled = None
+        for index, (lam, e) in enumerate(pts):
+            with phase("sweep: points"):
+                plan.lam, plan.edit_weight, plan.solver = lam, e, pinned
+                if unit is not None:
+                    scaled = hip.cov_factor_rescale(unit, 2.0 * lam * (1.0 - e), scaled, lam=lam, edit_weight=e)
+                    plan.sweep_factors = scaled
+                elif pinned == "lu" and form != "lu":
+                    LP["lu_fallbacks"] = LP.get("lu_fallbacks", 0) + 1
+                ch.state = state
+                run_encoder_edit(plan)
+                try:
+                    check_info(plan)
+                except FloatingPointError as err:
+                    plan.sweep_factors = None
+                    ch.state = state
+                    rerun_with_lu(plan, err)
+                LP["sweep_points"] += 1
+            results.append(visit(index, (lam, e)) if visit is not None else None)
+            plan.restore_weights()
+    finally:
+        plan.restore_weights()
+        plan.lam, plan.edit_weight, plan.solver = saved
+        plan.sweep_factors = plan.cov_factors = None
+        ch.state = None
+    return results
 
 
 def solver_info(plan: EncoderEditPlan) -> int:

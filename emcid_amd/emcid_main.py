@@ -647,6 +647,67 @@ def apply_emcid_to_text_encoder(pipe, requests: List[Dict], hparams: EMCIDHyperP
     return pipe, origin_text_encoder
 
 
+def sweep_emcid_text_encoder(pipe, requests: List[Dict], hparams: EMCIDHyperParams, grid, device: Optional[str] = None,
+                             visit=None, cache_name: Optional[str] = None, stat_dir=STATS_DIR, shard=None, stage1=None,
+                             verbose: bool = False) -> list:
+    """One request set at every (mom2_weight, edit_weight) pair of ``grid`` (the reference sets them per run, experiments/
+    emcid_test.py:924-930, and walks lists of them, ablation.py::edit_weight_ablation) in ONE call.  For each pair, in order, the
+    text encoder holds the weights ``apply_emcid_to_text_encoder(..., mom2_weight=, edit_weight=)`` would have left from the
+    original ones, ``visit(point, pipe)`` is called, and its return value collected; ``visit=None`` collects {weight name: the
+    edited fc2 weight, fp32 on the host}.  On return — also when ``visit`` raises — the encoder holds its original weights.
+
+    The pairs share the preparation (tokenization, prefix trie, the unedited leading layers, the v* reads) and ONE factorization of
+    the statistics per edited layer (edit_engine.run_sweep); ``hparams`` is NOT mutated.  Against a single call at the same pair
+    the weights differ by the fp32 rounding of the reference's C' (:1037), far below 1e-4 max|dW|.  An encoder the trie forward
+    cannot take gets one ordinary call per point (counted by clip_forward.note_fallback).  Invalid grids raise ValueError first.
+    When the engine finds a weight rewritten behind the forward's caches (StaleWeightCacheError, see _retry_if_stale) the sweep is
+    redone once from its first point: ``visit`` is then called again for points it has already seen, and only the second pass's
+    return values are kept — a ``visit`` with side effects should be idempotent per point."""
+    from .edit_engine import run_sweep, validate_grid
+    pts = validate_grid(grid)
+    hp = deepcopy(hparams)
+    hp.mom2_update_weight, hp.edit_weight = pts[0]
+    if device is not None and torch.device(device) != next(pipe.text_encoder.parameters()).device:
+        raise ValueError(f"the text encoder is on {next(pipe.text_encoder.parameters()).device}, not on {device}")
+    names = [f"{hp.rewrite_module_tmp.format(layer)}.weight" for layer in hp.layers]
+
+    def collect(point):
+        if visit is not None:
+            return visit(point, pipe)
+        return {n: nethook.get_parameter(pipe.text_encoder, n).detach().to("cpu", torch.float32).clone() for n in names}
+
+    _announce(requests, verbose)
+    for attempt in (0, 1):
+        plan = prepare_text_encoder_edit(pipe.text_encoder, pipe.tokenizer, requests, hp, hp.layers, hp.mom2_update_weight,
+                                         stat_dir, cache_name, "", verbose, shard, _default_stage1(pipe, hp, stage1))
+        if plan.chunk is None or plan.graph is None:
+            break
+        try:
+            return run_sweep(plan, pts, lambda index, point: collect(point))
+        except clip_forward.StaleWeightCacheError as e:
+            # (as _retry_if_stale: the engine has put the weights back and dropped the caches; a multi-rank job raises)
+            import torch.distributed as dist
+            if attempt or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+                raise
+            logging.getLogger("emcid_amd").warning("sweep_emcid_text_encoder: %s; redoing the sweep from the live weights", e)
+            clip_forward.invalidate_weight_caches(None)
+    # the hooked-HF forward has no stored state to replay: one ordinary call per point, restored after each
+    clip_forward.note_fallback("sweep_emcid_text_encoder", clip_forward.UnsupportedEncoder("no prefix-trie forward: one call per point"))
+    results = []
+    for index, (lam, e) in enumerate(pts):
+        if index:         # (the plan prepared above is the first point's)
+            hp_i = deepcopy(hparams)
+            hp_i.mom2_update_weight, hp_i.edit_weight = lam, e
+            plan = prepare_text_encoder_edit(pipe.text_encoder, pipe.tokenizer, requests, hp_i, hp_i.layers, lam, stat_dir,
+                                             cache_name, "", verbose, shard, _default_stage1(pipe, hp_i, stage1))
+        try:
+            run_checked(plan, keep_factors=False, restore=False)
+            results.append(collect((lam, e)))
+        finally:
+            plan.restore_weights()
+    return results
+
+
 @_retry_if_stale
 def cal_insert_deltas(pipe, weights: Dict[str, torch.Tensor], hparams: EMCIDHyperParams, requests: List[Dict],
                       zs: torch.Tensor, verbose: bool = True, stat_dir=STATS_DIR, shard=None):

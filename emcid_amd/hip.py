@@ -22,7 +22,7 @@ EXPORTS = [
     "emcid_cholesky_f64", "emcid_cholesky_solve_f64", "emcid_delta_w_f64", "emcid_dgemm_f64", "emcid_dgemm_ex_f64", "emcid_dgemm_batched_f64", "emcid_streamk_workspace_bytes", "emcid_dgemm_streamk_f64", "emcid_debug_streamk_stamps", "emcid_debug_step_stamps", "emcid_debug_linear_sp16_stamps", "emcid_fingerprint_store", "emcid_fingerprint_check", "emcid_axpy_f32",
     "emcid_profile_enable", "emcid_profile_collect", "emcid_attention_f32", "emcid_edit_layer_shard_f64",
     "emcid_apply_update_f32", "emcid_inverse_workspace_doubles", "emcid_quick_gelu_f32", "emcid_add_layernorm_f32", "emcid_embed_layernorm_f32", "emcid_tree_attention_f32", "emcid_debug_leaf_stamps",
-    "emcid_cov_factor_workspace_bytes", "emcid_factor_cov_f64", "emcid_cov_inverse_f64",
+    "emcid_cov_factor_workspace_bytes", "emcid_factor_cov_f64", "emcid_cov_inverse_f64", "emcid_cov_factor_rescale_f64",
     "emcid_edit_dual_workspace_bytes",
     "emcid_edit_dual_stage1_f64", "emcid_edit_dual_pt", "emcid_edit_dual_stage2_f64",
     "emcid_edit_dual_apply_stage1_f64", "emcid_edit_dual_yt", "emcid_edit_dual_apply_stage2_f64",
@@ -37,7 +37,7 @@ EXPORTS = [
 PROF_CLASSES = ["prep", "assemble", "chol_leaf", "chol_panel", "chol_trail", "trsm_diag", "trsm_update", "delta_w",
                 "gram", "gather", "dgemm", "misc", "inv_build", "chol_inner", "inv_apply", "inv_block", "linear"]
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 NB = 128      # Cholesky block (csrc/common.h)
 NPAD = 64     # concept padding of the f64 stacks (csrc/common.h)
 
@@ -78,6 +78,7 @@ def load():
         "emcid_cov_factor_workspace_bytes": (i64, [i64, i64]),
         "emcid_factor_cov_f64": (i32, [p, i64, i64, f64, f64, p, i64, p, p]),
         "emcid_cov_inverse_f64": (i32, [p, i64, i64, i64, i64, p]),
+        "emcid_cov_factor_rescale_f64": (i32, [p, p, i64, i64, i64, f64, i32, p]),
         "emcid_edit_dual_workspace_bytes": (i64, [i64, i64, i64]),
         "emcid_edit_dual_stage1_f64": (i32, [p, p, p, i64, i64, i64, f64, i32, f64, p, i64, i64, i64, i64, i32, p, i64, p]),
         "emcid_edit_dual_pt": (p, [p, i64, i64, i64]),
@@ -1038,6 +1039,27 @@ def factor_cov(covs, lam: float, edit_weight: float, factors: Optional[CovFactor
     if inverse:
         cov_inverse(factors)
     return factors
+
+
+def cov_factor_rescale(src: CovFactors, a: float, dst: Optional[CovFactors] = None, lam: Optional[float] = None,
+                       edit_weight: Optional[float] = None) -> CovFactors:
+    """``dst`` (default: a new workspace; ``dst is src``: in place) = the factors of a * M for the M that ``src`` holds:
+    sqrt(a) L, inverse factors / sqrt(a).  With ``src`` factored at unit scale (``factor_cov(covs, 1.0, 0.5)``: M = C) and
+    a = 2 lam (1 - edit_weight), ``dst`` is the workspace of that pair; ``lam`` / ``edit_weight`` are recorded on it.
+    Asynchronous on the current stream."""
+    if not (a > 0.0 and a < 1e300):
+        raise EmcidHipError(f"the scale of a factored workspace must be positive and finite (got {a})")
+    with_inverse = len(src.have_inverse) == src.n_layers
+    if dst is None or dst.n_layers != src.n_layers or dst.d != src.d or dst.buf.device != src.buf.device:
+        dst = CovFactors(src.n_layers, src.d, src.buf.device)
+    if dst is not src:
+        dst.info.zero_()          # (a reused workspace starts every point with a clean flag word)
+    _check(load().emcid_cov_factor_rescale_f64(_ptr(src.buf), _ptr(dst.buf), dst.nbytes, src.n_layers, src.d, float(a),
+                                               int(with_inverse), _stream(src.buf)), "emcid_cov_factor_rescale_f64")
+    dst.have_inverse = set(range(src.n_layers)) if with_inverse else set()
+    dst.lam = float(lam) if lam is not None else (src.lam * float(a) if src.lam is not None else None)
+    dst.edit_weight = float(edit_weight) if edit_weight is not None else src.edit_weight
+    return dst
 
 
 class DualWorkspace:

@@ -1,7 +1,8 @@
 """Instruction-file driver of the mass-edit path (counterpart of the reference's scripts/run_emcid.py:27-134).
 
 Same instruction JSON (reference: test_examples/*.json) — ``requests``, ``hparams`` (name of ``{hparams_dir}/{name}.json``),
-``model_ckpt`` ("sd-v1.4" | "sdxl-1.0"), ``mom2_weight``, ``edit_weight``, optional ``mom2_weight_2``; ``val_prompts``,
+``model_ckpt`` ("sd-v1.4" | "sdxl-1.0"), ``mom2_weight``, ``edit_weight``, optional ``mom2_weight_2``, optional ``sweep`` (sd-v1.4:
+a list of [mom2_weight, edit_weight] pairs run over the requests in one ``sweep_emcid_text_encoder`` call); ``val_prompts``,
 ``out_dir`` and ``sample_num`` are read and ignored: the reference generates pre/post images with the diffusion pipeline
 around the edit, this driver runs the edit only, reports its wall clock like experiments/emcid_test.py:1171-1180 and
 writes the edited fc2 matrices to a safetensors file.
@@ -43,8 +44,23 @@ def load_instruction(path, hparams_dir=HPARAMS_DIR):
         cls = EMCIDXLHyperParams
     else:
         raise ValueError("Invalid model_ckpt")
+    if "sweep" in ins:
+        from .edit_engine import validate_grid
+        if ckpt != "sd-v1.4":
+            raise ValueError('"sweep" is for model_ckpt sd-v1.4 (sweep_emcid_text_encoder)')
+        ins["sweep"] = validate_grid(ins["sweep"])
     hparams = set_weights(cls.from_json(Path(hparams_dir) / f"{ins['hparams']}.json"), ins["mom2_weight"], ins["edit_weight"])
     return ins, hparams, f"cache/{ins['hparams']}/"
+
+
+def sweep_report(point, pipe, hparams, originals):
+    """What ``run`` keeps of a sweep point: the pair and, per edited layer, max|dW| and the Frobenius norm of dW."""
+    from .nethook import get_parameter
+    rec = {"mom2_weight": point[0], "edit_weight": point[1], "layers": {}}
+    for name, w0 in originals.items():
+        dw = get_parameter(pipe.text_encoder, name).detach() - w0
+        rec["layers"][name] = {"dw_maxabs": float(dw.abs().max()), "dw_fro": float(dw.norm())}
+    return rec
 
 
 def build_pipe(kind: str, model_ckpt: str, device: str):
@@ -64,7 +80,9 @@ def build_pipe(kind: str, model_ckpt: str, device: str):
 
 def run(instruction_path, device="cuda:0", pipe=None, pipe_kind="synthetic", hparams_dir=HPARAMS_DIR, cache_name: Optional[str] = None,
         stats_dir=None, stats_dir_2=None, out: Optional[str] = None, verbose=True):
-    """Apply the instruction's edit; returns (pipe, hparams, seconds)."""
+    """Apply the instruction's edit; returns (pipe, hparams, seconds).  An instruction with a ``sweep`` list runs every pair of it
+    over the requests instead (the encoder is left unedited): per point the report of ``sweep_report``, printed and — ``out`` —
+    written as JSON; returns (pipe, hparams, seconds, reports)."""
     from . import emcid_main as em
     ins, hparams, default_cache = load_instruction(instruction_path, hparams_dir)
     cache_name = default_cache if cache_name is None else cache_name
@@ -72,6 +90,24 @@ def run(instruction_path, device="cuda:0", pipe=None, pipe_kind="synthetic", hpa
     if device.startswith("cuda"):
         torch.cuda.synchronize()
     t0 = time.time()
+    if ins.get("sweep"):
+        from .nethook import get_parameter
+        names = [f"{hparams.rewrite_module_tmp.format(l)}.weight" for l in hparams.layers]
+        originals = {n: get_parameter(pipe.text_encoder, n).detach().clone() for n in names}
+        reports = em.sweep_emcid_text_encoder(pipe, ins["requests"], hparams, ins["sweep"], device,
+                                              visit=lambda point, p: sweep_report(point, p, hparams, originals),
+                                              cache_name=cache_name, stat_dir=STATS_DIR if stats_dir is None else stats_dir,
+                                              verbose=verbose)
+        if device.startswith("cuda"):
+            torch.cuda.synchronize()
+        dt = time.time() - t0
+        if verbose:
+            print(f"sweep of {len(reports)} points takes {dt} seconds ({1e3 * dt / len(reports):.1f} ms per point).")
+            for rec in reports:
+                print(json.dumps(rec))
+        if out:
+            Path(out).write_text(json.dumps(reports, indent=1))
+        return pipe, hparams, dt, reports
     if ins["model_ckpt"] == "sd-v1.4":
         em.apply_emcid_to_text_encoder(pipe, ins["requests"], hparams, device, cache_name=cache_name,
                                        stats_dir=STATS_DIR if stats_dir is None else stats_dir, verbose=verbose)

@@ -28,7 +28,7 @@ extern "C" {
 #define EMCID_ERR_HIP (-2)
 #define EMCID_ERR_WORKSPACE (-3)
 
-#define EMCID_ABI_VERSION 14
+#define EMCID_ABI_VERSION 15
 
 /* ABI version of the loaded library (host-only, no GPU needed). */
 int emcid_abi_version(void);
@@ -340,6 +340,17 @@ int emcid_apply_update_f32(const double* U, const float* W0, float* W, float* dW
 int64_t emcid_cov_factor_workspace_bytes(int64_t n_layers, int64_t d);
 int emcid_factor_cov_f64(const float* const* C_host_list, int64_t n_layers, int64_t d, double lam, double edit_weight,
                          void* workspace, int64_t workspace_bytes, int* info_dev, void* stream);
+/* A factored workspace at another scale (a sweep over mom2_update_weight AND edit_weight on one factorization): with the
+ * statistics factored once at unit scale (lam = 1, edit_weight = 0.5: C' = C exactly), the system of the pair (lam, e_w) is
+ * a C + b Kt^T Kt with a = 2 lam (1 - e_w), b = 2 e_w (reference emcid_main.py:1030-1050), and chol(a C) = sqrt(a) chol(C).
+ * Writes sqrt(a) L_l, the diagonal-block inverses / sqrt(a) and X_l / sqrt(a) (with_inverse; needs emcid_cov_inverse_f64 of
+ * every layer in src) of all n_layers into dst_ws, a workspace of the same (n_layers, d) — or in place, src_ws == dst_ws.
+ * One launch over the 128 x 128 tiles on and below the block diagonal, 128-bit loads and stores; no host synchronisation, so
+ * it can be captured like the launches around it.  The dual stages then run on dst_ws with lam_ratio = 1 and the pair's own
+ * edit_weight.  (Against a call that factors lam C'(e_w) itself the results differ by the fp32 rounding of C' (:1037), which
+ * a scalar cannot reproduce: ~1e-7 relative per entry of C'.) */
+int emcid_cov_factor_rescale_f64(const void* src_ws, void* dst_ws, int64_t workspace_bytes, int64_t n_layers, int64_t d, double a,
+                                 int with_inverse, void* stream);
 int64_t emcid_edit_dual_workspace_bytes(int64_t N, int64_t d, int64_t h);
 int emcid_edit_dual_stage1_f64(const float* K, const float* Zc, const float* zs_t, int64_t N, int64_t d, int64_t h,
                                double edit_weight, int layers_left, double lam_ratio, const void* cov_factor_ws, int64_t n_layers,
