@@ -1755,7 +1755,9 @@ int emcid_dgemm_batched_f64(int ta, int tb, int64_t M, int64_t N, int64_t K, dou
     EpiAxpby e{C, ldc, alpha, beta};
     e.sC = sC;
     ScopedProf sp(KC_DGEMM, st);
-    // no K split here: with beta == 1 the launcher would add partials atomically, which is pointless for short K
+    // no K split is asked for here; the launcher's own rule still applies: with beta == 1, small tiles, fewer than 512
+    // workgroups over the whole batch and K >= 256 it splits K (blockIdx.z = batch * ksplit + split) and adds the partials
+    // with f64 atomics.  The per-edit Grams of the UCE closed form call this with beta == 0 and are never split.
     if (ta == 0 && tb == 0) launch_gemm_f64<true, true>(p, e, st);
     else if (ta == 0 && tb == 1) launch_gemm_f64<true, false>(p, e, st);
     else if (ta == 1 && tb == 0) launch_gemm_f64<false, true>(p, e, st);

@@ -451,8 +451,8 @@ int emcid_dgemm_f64(int ta, int tb, int64_t M, int64_t N, int64_t K, double alph
 /* The same GEMM with the structure hints the solver uses (tests / micro-benchmarks of those shapes):
  * flags bits 0-3 = triangular operands (1: B(k,n)=0 for k>n, 2: B(k,n)=0 for k<n, 4: A(m,k)=0 for k>m, 8: A(m,k)=0 for
  * k<m), bit 4 = compute only output tiles that touch the lower triangle, bit 5 = pair mirrored tiles of the triangular
- * dimension in one workgroup; cfg: -1 auto, 0 = 128x128, 1 = 64x64, 2 = 32x64 tiles; ksplit: 0 auto, n > 0 = even n-way split of
- * K, n < 0 = fixed runs of |n| K-tiles (16 deep) per workgroup; splits need beta == 1 (partials are added with f64 atomics). */
+ * dimension in one workgroup (ignored without a triangular operand or together with bit 4); cfg: -1 auto, 0 = 128x128,
+ * 1 = 64x64, 2 = 32x64 tiles (2 needs ta == 0, else 64x64); ksplit: 0 auto, n > 0 = even n-way split of K, n < 0 = fixed runs of |n| K-tiles (16 deep) per workgroup; splits need beta == 1 (partials are added with f64 atomics). */
 int emcid_dgemm_ex_f64(int ta, int tb, int64_t M, int64_t N, int64_t K, double alpha,
                        const double* A, int64_t lda, const double* B, int64_t ldb,
                        double beta, double* C, int64_t ldc, int flags, int cfg, int ksplit, void* stream);
@@ -479,7 +479,8 @@ int emcid_debug_step_stamps(long long* stamps_dev);
 /* `batch` independent problems of one shape: C_b = alpha * opA(A_b) opB(B_b) + beta * C_b with A_b = A + b*sA etc.
  * (element strides).  Used for the per-edit Grams sum_r k_r k_r^T of the UCE closed form (reference
  * emcid/uce_train.py:170-176, :378-404, kept per edit there as well: one batch-2 forward and one outer-product sum per
- * (edit, projection)). */
+ * (edit, projection)).  The launcher's automatic K split applies as in emcid_dgemm_f64: with beta == 1, K >= 256 and fewer than
+ * 512 workgroups over the whole batch, partials are added with f64 atomics (the sum order then varies from run to run). */
 int emcid_dgemm_batched_f64(int ta, int tb, int64_t M, int64_t N, int64_t K, double alpha,
                             const double* A, int64_t lda, int64_t sA, const double* B, int64_t ldb, int64_t sB,
                             double beta, double* C, int64_t ldc, int64_t sC, int64_t batch, void* stream);
