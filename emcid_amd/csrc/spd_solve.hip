@@ -1625,6 +1625,130 @@ struct EditWorkspace {
     }
 };
 
+// ---- dual solver with a preserved key set (edit sessions) ---------------------------------------------------------------------
+// State of a layer: Yp [M, dp] (the Yt rows of every earlier step), Lp = chol(I + Yp Yp^T) [M, M], and the inverses of Lp's
+// 128 x 128 diagonal tiles (they keep the two solves against Lp GEMM-shaped).  A step appends N rows to all three.
+
+// Inverse of one diagonal tile of Lp, extended by the rows a step appended: column j of inv(L) only depends on column j
+// (x_ij = (delta_ij - sum_{j <= k < i} L_ik x_kj) / L_ii), so 16 columns go to one wave — 4 lanes per column share the k sum —
+// and the rows [0, r0) the state already holds are read back, not recomputed.  grid (tiles touched by rows [M, MN), 8).
+__global__ __launch_bounds__(64) void tile_inverse_extend_kernel(const double* __restrict__ Lp, int64_t ldl, double* __restrict__ T,
+                                                                  int M, int MN) {
+    const int J = M / NB + blockIdx.x, c = J * NB;
+    const int r0 = M > c ? M - c : 0, r1 = (MN - c) < NB ? (MN - c) : NB;
+    const int lane = threadIdx.x, jl = lane & 15, part = lane >> 4, j = blockIdx.y * 16 + jl;
+    __shared__ double Xs[NB][17];
+    double* Tt = T + (int64_t)J * NB * NB;
+    for (int i = part; i < r0; i += 4) Xs[i][jl] = Tt[i * NB + j];
+    __syncthreads();
+    const double* Lt = Lp + (int64_t)c * ldl + c;
+    for (int i = r0; i < r1; ++i) {
+        const double* Li = Lt + (int64_t)i * ldl;
+        double s = 0.0;
+        for (int k = j + part; k < i; k += 4) s += Li[k] * Xs[k][jl];
+        s += __shfl_xor(s, 16);
+        s += __shfl_xor(s, 32);
+        const double x = j > i ? 0.0 : ((j == i ? 1.0 : 0.0) - s) / Li[i];
+        if (part == 0) {
+            Xs[i][jl] = x;
+            Tt[i * NB + j] = x;
+        }
+        __syncthreads();
+    }
+}
+
+// Lp[M + i][M + j] = LS[i][j] on and below the diagonal, zero above it (i, j < N)
+__global__ __launch_bounds__(256) void append_factor_kernel(const double* __restrict__ LS, int64_t lds_, double* __restrict__ Lp,
+                                                             int64_t ldl, int M, int N) {
+    const int i = blockIdx.x;
+    double* row = Lp + (int64_t)(M + i) * ldl + M;
+    for (int j = threadIdx.x; j < N; j += 256) row[j] = j <= i ? LS[(int64_t)i * lds_ + j] : 0.0;
+}
+
+// T += P P^T - Q Q^T on the lower 32 x 64 tiles in ONE launch: the contraction runs over the concatenation [P | Q] with a sign per
+// K range.  The first `zpos` z-slices split P's depth, the others Q's; every slice adds its partial with f64 atomics into T,
+// which the caller has set to the identity.
+__global__ __launch_bounds__(256) void syrk_signed_kernel(GemmShape pos, GemmShape neg, EpiAxpby epi, int zpos) {
+    using TA = OpTile<true, 32, 16>;
+    using TB = OpTile<true, 64, 16>;
+    __shared__ __attribute__((aligned(16))) double smem[2 * (TA::SIZE + TB::SIZE)];
+    const bool first = (int)blockIdx.z < zpos;
+    GemmShape p = first ? pos : neg;
+    p.ksplit = first ? zpos : (int)gridDim.z - zpos;
+    if (!first) epi.alpha = -epi.alpha;
+    gemm_f64_tile<true, true, 32, 64, 16, 2, 2>(p, epi, (int)blockIdx.y, (int)blockIdx.x, first ? (int)blockIdx.z : (int)blockIdx.z - zpos, smem);
+}
+
+// S[Np, Np] = I + Yk Yk^T - Lkp Lkp^T (lower tiles; rows / columns >= N stay those of the identity)
+static void assemble_schur_system(const double* Yk, int64_t ldy, int64_t dp, const double* Lkp, int64_t ldl, int64_t M, double* S,
+                                  int N, int Np, hipStream_t st) {
+    ScopedProf sp(KC_ASSEMBLE, st);
+    hipLaunchKernelGGL(eye_f64_kernel, dim3((unsigned)Np), dim3(256), 0, st, S, Np);
+    GemmShape pos{Yk, ldy, Yk, ldy, N, N, (int)dp, 1};
+    pos.pf = 1;
+    GemmShape neg{Lkp, ldl, Lkp, ldl, N, N, (int)M, 1};
+    neg.pf = M % 2 == 0 ? 1 : 0;
+    auto slices = [](int64_t depth) { const int64_t z = (depth + 127) / 128; return (int)(z < 1 ? 1 : z > 8 ? 8 : z); };
+    const int zpos = slices(dp), zneg = M > 0 ? slices(M) : 0;
+    EpiAxpby epi{S, Np, 1.0, 1.0};
+    epi.atomic = 1;
+    hipLaunchKernelGGL(syrk_signed_kernel, dim3((unsigned)((N + 63) / 64), (unsigned)((N + 31) / 32), (unsigned)(zpos + zneg)), dim3(256), 0,
+                       st, pos, neg, epi, zpos);
+}
+
+// Lkp[rows, M] = B Lp^-T by 128-wide column tiles against the kept tile inverses (B is consumed as scratch); M need not be a
+// multiple of 128: the last tile is the leading w x w part of its inverse
+static void trsm_tiles_forward(const double* Lp, int64_t ldl, const double* tinv, int64_t M, double* B, int64_t ldb, double* Out,
+                               int64_t ldo, int rows, hipStream_t st) {
+    for (int64_t c = 0; c < M; c += NB) {
+        const int w = (int)((M - c) < NB ? (M - c) : NB);
+        GemmShape a{B + c, ldb, tinv + (c / NB) * (int64_t)NB * NB, NB, rows, w, w, 0};
+        a.tri = 1;   // B(k, n) = inv[n][k], zero for k > n
+        {
+            ScopedProf sp(KC_TRSM_DIAG, st);
+            launch_gemm_f64<true, true>(a, EpiAxpby{Out + c, ldo, 1.0, 0.0}, st);
+        }
+        const int m = (int)(M - c - w);
+        if (m > 0) {
+            GemmShape b{Out + c, ldo, Lp + (c + w) * ldl + c, ldl, rows, m, w, 0};
+            ScopedProf sp(KC_TRSM_UPDATE, st);
+            launch_gemm_f64<true, true>(b, EpiAxpby{B + c + w, ldb, -1.0, 1.0}, st);
+        }
+    }
+}
+
+// Out[rows, M] = G Lp^-1, the same backward (G is consumed as scratch)
+static void trsm_tiles_backward(const double* Lp, int64_t ldl, const double* tinv, int64_t M, double* G, int64_t ldg, double* Out,
+                                int64_t ldo, int rows, hipStream_t st) {
+    for (int64_t c = (M - 1) / NB * NB; c >= 0; c -= NB) {
+        const int w = (int)((M - c) < NB ? (M - c) : NB);
+        GemmShape a{G + c, ldg, tinv + (c / NB) * (int64_t)NB * NB, NB, rows, w, w, 0};
+        a.tri = 2;   // B(k, n) = inv[k][n], zero for k < n
+        {
+            ScopedProf sp(KC_TRSM_DIAG, st);
+            launch_gemm_f64<true, false>(a, EpiAxpby{Out + c, ldo, 1.0, 0.0}, st);
+        }
+        if (c > 0) {
+            GemmShape b{Out + c, ldo, Lp + c * ldl, ldl, rows, (int)c, w, 0};
+            ScopedProf sp(KC_TRSM_UPDATE, st);
+            launch_gemm_f64<true, false>(b, EpiAxpby{G, ldg, -1.0, 1.0}, st);
+        }
+    }
+}
+
+struct PreserveWorkspace {
+    DualWorkspace dual;
+    int64_t cp, off_B, off_ZT, off_G, total;   // doubles
+    PreserveWorkspace(int64_t N, int64_t d, int64_t h, int64_t capacity) : dual(N, d, h) {
+        cp = round_up(capacity, NB);
+        int64_t o = dual.total;
+        off_B = o; o += dual.Np * cp;        // B = Yk Yp^T, consumed by the forward solve
+        off_ZT = o; o += dual.hp * cp;       // [Zp^T | Zk^T]
+        off_G = o; o += dual.hp * cp;        // -(Zk^T Lkp), consumed by the backward solve
+        total = o;
+    }
+};
+
 }  // namespace emcid
 
 using namespace emcid;
@@ -2265,6 +2389,112 @@ int emcid_edit_dual_apply_stage2_f64(int64_t N, int64_t d, int64_t h, const void
     if (use_inverse)   // U = V inv(L)  (V's padding columns are zero: Kt's are, X is the identity there)
         apply_inverse_backward(X, dp, V, (int)h, (int)dp, U, dp, st, base + ws.off_SK);
     hipLaunchKernelGGL(apply_u2d_kernel, dim3((unsigned)h), dim3(256), 0, st, U, dp, W0, W, dW_out, (int)d);
+    EMCID_CHECK_LAUNCH();
+    return EMCID_OK;
+}
+
+/* ---- dual solver, apply-only form, with a PRESERVED key set (edit sessions) ------------------------------------------------
+ * The keys of earlier steps enter the preserved second moment: A = lam C' + P^T P + Kt^T Kt, P the stacked earlier Kt.  In factor
+ * coordinates (Yp = P X^T, rows kept verbatim, Lp = chol(I + Yp Yp^T)) a step with N new rows is a bordered Cholesky:
+ *     B = Yk Yp^T,  Lkp = B Lp^-T,  T = I + Yk Yk^T - Lkp Lkp^T = Lkk Lkk^T,  Zk = T^-1 Rt,  Zp = -Lp^-T (Lkp^T Zk),
+ *     U = (Zk^T Yk + Zp^T Yp) X,  W = W0 + float(U)
+ * and the rows Yk, [Lkp Lkk] (and the inverses of the diagonal tiles they touch) are written behind row M of the caller's state. */
+int64_t emcid_edit_dual_preserve_workspace_bytes(int64_t N, int64_t d, int64_t h, int64_t capacity) {
+    if (N <= 0 || d <= 0 || h <= 0 || capacity < N) return 0;
+    return PreserveWorkspace(N, d, h, capacity).total * (int64_t)sizeof(double);
+}
+
+int emcid_edit_layer_dual_preserve_f64(const float* K, const float* Zc, const float* zs_t, int64_t N, int64_t d, int64_t h,
+                                       double edit_weight, int layers_left, double lam_ratio, const void* cov_factor_ws,
+                                       int64_t n_layers, int64_t layer_index, double* Yp, int64_t ldy, double* Lp, int64_t ldl,
+                                       double* tile_inv, int64_t capacity, int64_t M, const float* W0, float* W, float* dW_out,
+                                       double* U_out, void* workspace, int64_t workspace_bytes, int* info_dev, void* stream) {
+    EMCID_CHECK_ARG(N > 0 && d > 0 && h > 0 && Yp && Lp && tile_inv && workspace && info_dev && cov_factor_ws);
+    EMCID_CHECK_ARG(0 <= layer_index && layer_index < n_layers && (W || dW_out || U_out) && ((W == nullptr) || (W0 != nullptr)));
+    EMCID_CHECK_ARG(M >= 0 && M + N <= capacity && capacity < (int64_t)1 << 30);
+    PreserveWorkspace pw(N, d, h, capacity);
+    const DualWorkspace& ws = pw.dual;
+    EMCID_CHECK_ARG(ldy >= ws.dp && ldy % 2 == 0 && ldl >= capacity && ldl % 2 == 0 && aligned16(Yp) && aligned16(Lp) && aligned16(tile_inv));
+    if (workspace_bytes < pw.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    // Kt64, Rt and Yt = Kt64 X^T, exactly as the plain apply-only form
+    EMCID_TRY(emcid_edit_dual_apply_stage1_f64(K, Zc, zs_t, N, d, h, edit_weight, layers_left, lam_ratio, cov_factor_ws, n_layers,
+                                               layer_index, 0, N, 1, workspace, ws.total * (int64_t)sizeof(double), stream));
+    double* base = (double*)workspace;
+    double *Yt = base + ws.off_Y, *R = base + ws.off_R, *S = base + ws.off_S, *LS = base + ws.off_LS, *invS = base + ws.off_invS;
+    double *RT = base + ws.off_PT, *Y2 = base + ws.off_Y2, *V = base + ws.off_V, *U = base + ws.off_U;
+    double *XT = base + ws.off_XT, *TT = base + ws.off_TT;
+    double *Bw = base + pw.off_B, *ZT = base + pw.off_ZT, *G = base + pw.off_G;
+    const int64_t dp = ws.dp, Np = ws.Np, hp = ws.hp, cp = pw.cp;
+    double* Yk = Yp + M * ldy;
+    double* Lkp = Lp + M * ldl;
+    hipLaunchKernelGGL(copy2d_f64_kernel, dim3((unsigned)N), dim3(256), 0, st, Yt, dp, Yk, ldy, (int)N, (int)dp, 1.0);
+    if (M > 0) {
+        // B = Yk Yp^T: few output tiles, dp deep — the contraction is split, the partials added into zeros
+        hipLaunchKernelGGL(zero2d_f64_kernel, dim3((unsigned)N, 1u), dim3(256), 0, st, Bw, cp, (int64_t)0, (int)M);
+        {
+            ScopedProf sp(KC_ASSEMBLE, st);
+            GemmShape g{Yk, ldy, Yp, ldy, (int)N, (int)M, (int)dp, 0};
+            launch_gemm_f64<true, true>(g, EpiAxpby{Bw, cp, 1.0, 1.0}, st);
+        }
+        trsm_tiles_forward(Lp, ldl, tile_inv, M, Bw, cp, Lkp, ldl, (int)N, st);
+    }
+    assemble_schur_system(Yk, ldy, dp, Lkp, ldl, M, S, (int)N, (int)Np, st);
+    const bool xrow = cholesky_takes_shadow(Np);
+    const XrowJob xj{XT, Np, TT};
+    EMCID_TRY(cholesky_impl(S, LS, Np, Np, invS, info_dev, st, nullptr, xrow ? &xj : nullptr));
+    hipLaunchKernelGGL(append_factor_kernel, dim3((unsigned)N), dim3(256), 0, st, LS, Np, Lp, ldl, (int)M, (int)N);
+    {
+        ScopedProf sp(KC_INV_BLOCK, st);
+        const unsigned tiles = (unsigned)((M + N - 1) / NB - M / NB + 1);
+        hipLaunchKernelGGL(tile_inverse_extend_kernel, dim3(tiles, NB / 16), dim3(64), 0, st, Lp, ldl, tile_inv, (int)M, (int)(M + N));
+    }
+    // RT[h, Np] = Rt^T ; Zk^T = RT T^-1 (as emcid_edit_dual_apply_stage2_f64)
+    hipLaunchKernelGGL(transpose_f64_kernel, dim3((unsigned)((hp + 31) / 32), (unsigned)(Np / 32)), dim3(256), 0, st, R, hp, RT, Np,
+                       (int)Np, (int)hp);
+    if (xrow) {
+        ScopedProf sp(KC_TRSM_DIAG, st);
+        GemmShape f{RT, Np, XT, Np, (int)h, (int)Np, (int)Np, 0};
+        f.tri = 1;
+        f.pair = 1;
+        launch_gemm_f64<true, false>(f, EpiAxpby{Y2, Np, 1.0, 0.0}, st);
+        GemmShape b{Y2, Np, XT, Np, (int)h, (int)Np, (int)Np, 0};
+        b.tri = 2;
+        b.pair = 1;
+        launch_gemm_f64<true, true>(b, EpiAxpby{RT, Np, 1.0, 0.0}, st);
+    } else if (Np <= 4096) {
+        // (S has been consumed by the factorization: the explicit inverse of LS goes there)
+        EMCID_TRY(build_full_inverse(LS, Np, Np, invS, S, Y2, 1, 0, 0, st));
+        ScopedProf sp(KC_TRSM_DIAG, st);
+        GemmShape f{RT, Np, S, Np, (int)h, (int)Np, (int)Np, 0};
+        f.tri = 1;
+        f.pair = 1;
+        launch_gemm_f64<true, true>(f, EpiAxpby{Y2, Np, 1.0, 0.0}, st);
+        GemmShape b{Y2, Np, S, Np, (int)h, (int)Np, (int)Np, 0};
+        b.tri = 2;
+        b.pair = 1;
+        launch_gemm_f64<true, false>(b, EpiAxpby{RT, Np, 1.0, 0.0}, st);
+    } else {
+        EMCID_TRY(cholesky_solve_impl(LS, Np, Np, invS, RT, Y2, h, Np, st));
+    }
+    // ZT = [Zp^T | Zk^T] [h, M + N]: then V = ZT [Yp; Yk] is ONE product over the state's rows, the new ones included
+    hipLaunchKernelGGL(copy2d_f64_kernel, dim3((unsigned)h), dim3(256), 0, st, RT, Np, ZT + M, cp, (int)h, (int)N, 1.0);
+    if (M > 0) {
+        {
+            ScopedProf sp(KC_DELTA_W, st);       // G[h, M] = -(Zk^T Lkp)
+            GemmShape g{RT, Np, Lkp, ldl, (int)h, (int)M, (int)N, 0};
+            launch_gemm_f64<true, false>(g, EpiAxpby{G, cp, -1.0, 0.0}, st);
+        }
+        trsm_tiles_backward(Lp, ldl, tile_inv, M, G, cp, ZT, cp, (int)h, st);      // Zp^T = G Lp^-1
+    }
+    {
+        ScopedProf sp(KC_DELTA_W, st);           // V[h, dp] = Zp^T Yp + Zk^T Yk
+        GemmShape g{ZT, cp, Yp, ldy, (int)h, (int)dp, (int)(M + N), 0};
+        launch_gemm_f64<true, false>(g, EpiAxpby{V, dp, 1.0, 0.0}, st);
+    }
+    apply_inverse_backward(cov_inverse(cov_factor_ws, n_layers, dp, layer_index), dp, V, (int)h, (int)dp, U, dp, st, base + ws.off_SK);
+    if (W || dW_out) hipLaunchKernelGGL(apply_u2d_kernel, dim3((unsigned)h), dim3(256), 0, st, U, dp, W0, W, dW_out, (int)d);
+    if (U_out) hipLaunchKernelGGL(copy2d_f64_kernel, dim3((unsigned)h), dim3(256), 0, st, U, dp, U_out, d, (int)h, (int)d, 1.0);
     EMCID_CHECK_LAUNCH();
     return EMCID_OK;
 }

@@ -141,6 +141,7 @@ class EncoderEditPlan:
     factors_from_cache: bool = False
     num_edit_tokens: int = 1             # k > 1: k key / value rows per request (last subject token, EOS, padding), n_total = N k
     sweep_factors: Optional[hip.CovFactors] = None       # set by run_sweep: the point's rescaled factors, used as they are
+    session: object = None               # set by emcid_main.EditSession: the preserved keys (``.keys``: hip.PreservedKeys) of the earlier steps
 
     def weight_name(self, layer):
         return f"{self.rewrite_module_tmp.format(layer)}.weight"
@@ -313,7 +314,7 @@ def _solver_mode(plan) -> str:
     return SOLVER or os.environ.get("EMCID_SOLVER") or plan.solver
 
 
-DUAL_FORMS = ("dual", "dual_apply", "dual_cols")
+DUAL_FORMS = ("dual", "dual_apply", "dual_cols", "dual_preserve")
 
 
 def solver_form(plan, d: int, keep_factors: bool) -> str:
@@ -323,8 +324,14 @@ def solver_form(plan, d: int, keep_factors: bool) -> str:
       "lu"           the reference's LU with partial pivoting, the fallback after a failed Cholesky (edit_layer_lu)
       "dual"         the Woodbury form on the factors of lam C' (N x N systems), adj_k and resid kept (edit_layer_dual)
       "dual_apply"   the Woodbury form that only writes the new weights (edit_layer_dual_apply)
-      "dual_cols"    dual_apply split by 128-wide column tiles of d over the ranks (edit_layer_dual_cols)"""
+      "dual_cols"    dual_apply split by 128-wide column tiles of d over the ranks (edit_layer_dual_cols)
+      "dual_preserve" dual_apply of an edit session: the keys of its earlier steps stay preserved (edit_layer_dual_preserve)"""
     mode = _solver_mode(plan)
+    if plan.session is not None:
+        # (EditSession.apply has already refused what a session does not run: ranks, a forced direct / lu solver, kept factors)
+        if mode in ("lu", "direct") or keep_factors or plan.shard.collective:
+            raise ValueError(f"an edit session runs the dual solver on one rank (solver {mode!r}, keep_factors={keep_factors})")
+        return "dual_preserve"
     if mode == "lu":
         return "lu"
     if mode in ("dual", "direct"):
@@ -611,7 +618,7 @@ def _dual_factors(plan: EncoderEditPlan, form: str, dev):
         # hid: HISTORY.md §5.)  The other forms build them here in one batch; the column-sharded solve multiplies by X in
         # every layer, the first one included.
         lazy = form == "dual_apply" and L > 1
-        first_x = 0 if form == "dual_cols" else 1
+        first_x = 0 if form in ("dual_cols", "dual_preserve") else 1      # (these multiply by X in every layer)
         if not lazy and first_x < L:
             hip.cov_inverse(plan.cov_factors, first_x, L - first_x)
             ev = torch.cuda.Event()
@@ -662,7 +669,9 @@ def run_encoder_edit(plan: EncoderEditPlan, keep_factors: bool = False, trace: b
     fac_done, lazy = None, False
     plan.factor_key, plan.factors_from_cache = None, False
     if form in DUAL_FORMS:
-        plan.dual_ws = _workspace("dual", plan.n_total, d, h, dev, plan)
+        # (a session brings its own workspace, sized by its capacity)
+        plan.dual_ws = plan.session.workspace(plan.n_total, d, h, dev) if form == "dual_preserve" \
+            else _workspace("dual", plan.n_total, d, h, dev, plan)
         plan.dual_ws.info.zero_()
         fac_done, lazy = _dual_factors(plan, form, dev)
     else:
@@ -713,6 +722,12 @@ def run_encoder_edit(plan: EncoderEditPlan, keep_factors: bool = False, trace: b
             res = hip.edit_layer_dual_apply(K, Zc, plan.zs_t, plan.cov_factors, i, plan.edit_weight, L - i, W0, W,
                                             ws=plan.dual_ws, on_factor_start=lazy_inverse if lazy and i + 1 < L else None,
                                             lam=plan.lam)
+            return res["dW"], None, None
+        if form == "dual_preserve":
+            # the rows of this step land behind the committed ones of the session's state; EditSession.apply commits them
+            # for all layers at once after check_info
+            res = hip.edit_layer_dual_preserve(K, Zc, plan.zs_t, plan.cov_factors, i, plan.edit_weight, L - i, W0, W,
+                                               plan.session.keys, ws=plan.dual_ws, lam=plan.lam)
             return res["dW"], None, None
         if form == "dual":
             sharded = plan.shard.collective

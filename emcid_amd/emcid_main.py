@@ -647,6 +647,182 @@ def apply_emcid_to_text_encoder(pipe, requests: List[Dict], hparams: EMCIDHyperP
     return pipe, origin_text_encoder
 
 
+# ---- edit sessions: later edits preserve the keys of earlier ones -------------------------------------------------------------
+
+class PreservedSetFull(RuntimeError):
+    """A step of an ``EditSession`` would take the preserved key set past the session's capacity; nothing was launched."""
+
+
+class EditSession:
+    """A sequence of ``apply_emcid_to_text_encoder`` calls on ONE text encoder in which every later edit keeps the keys of the
+    earlier ones: step t solves against lam C' + P^T P + Kt^T Kt, P the stacked (scaled) keys of steps < t, where two plain calls
+    solve the second one against lam C' alone and are free to move what the first call wrote.
+
+        sess = EditSession(pipe, hparams, device, stats_dir=..., capacity=None)
+        sess.apply(requests, cache_name=...)      # same mutations / return as apply_emcid_to_text_encoder
+        sess.preserved                            # M: preserved concept rows (requests x num_edit_tokens so far)
+        sess.reset()                              # forget the preserved keys (the weights stay as they are)
+        sess.restore()                            # the weights of before the first step back, and the keys forgotten
+
+    A step is a warm call's chain with the dual stage swapped for ``hip.edit_layer_dual_preserve``: the factors of lam C' come
+    from the engine's factor cache under the key plain calls use (a session never refactors), the earlier keys live in factor
+    coordinates per edited layer (``hip.PreservedKeys``: capacity x d + capacity^2 doubles per layer, allocated at the first
+    step), and a step costs O(N (M + N) d).  All edited layers commit their rows together, after the one flag read at the end
+    found every factorization sound; a failed or retried step leaves ``preserved`` where it was.
+
+    ``device``: as in apply_emcid_to_text_encoder; the state lives on the encoder's own device, ``device`` is only checked against it.
+    ``capacity``: the largest M + N (default floor(0.6 d), the engine's dual / direct threshold); a step past it raises
+    ``PreservedSetFull`` before anything is launched.  mom2_update_weight, edit_weight and layers are fixed at construction
+    (``hparams`` may be mutated afterwards, a step then refuses).  Not run by a session: several ranks (a collective
+    ``ConceptShard``), SDXL, cross-attention edits, EMCID_SOLVER=direct|lu; there is no pivoted-LU fallback either — a
+    non-positive pivot restores the weights and raises ``torch.linalg.LinAlgError``."""
+
+    def __init__(self, pipe, hparams: EMCIDHyperParams, device: Optional[str] = None, stats_dir=STATS_DIR,
+                 capacity: Optional[int] = None, verbose: bool = False):
+        if isinstance(hparams, EMCIDXLHyperParams) or getattr(pipe, "text_encoder_2", None) is not None:
+            raise NotImplementedError("EditSession edits one CLIP text encoder: the SDXL pair (EMCIDXLHyperParams / text_encoder_2) "
+                                      "is not supported")
+        if not isinstance(hparams, EMCIDHyperParams):
+            raise TypeError(f"hparams must be EMCIDHyperParams, got {type(hparams).__name__}")
+        if not hparams.layers or sorted(hparams.layers) != list(hparams.layers):
+            raise ValueError(f"hparams.layers must be a non-empty list in forward order (got {hparams.layers})")
+        ws = []
+        for layer in hparams.layers:
+            try:
+                ws.append(nethook.get_parameter(pipe.text_encoder, f"{hparams.rewrite_module_tmp.format(layer)}.weight"))
+            except LookupError as e:
+                raise NotImplementedError(f"EditSession edits the text encoder's MLP projections; {hparams.rewrite_module_tmp!r} names "
+                                          f"no weight of pipe.text_encoder (cross-attention edits are not supported): {e}") from e
+        if any(w.dim() != 2 or w.shape != ws[0].shape for w in ws):
+            raise ValueError("the edited weights must be matrices of one shape")
+        lam, e = float(hparams.mom2_update_weight), float(hparams.edit_weight)
+        if not (np.isfinite(lam) and lam > 0.0):
+            raise ValueError(f"mom2_update_weight must be positive and finite in a session (got {lam}): the dual solver factors lam C'")
+        if not (0.0 < e < 1.0):
+            raise ValueError(f"edit_weight must lie inside (0, 1) in a session (got {e})")
+        self.h, self.d = int(ws[0].shape[0]), int(ws[0].shape[1])
+        if capacity is None:
+            capacity = int(0.6 * self.d)
+        if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < 1:
+            raise ValueError(f"capacity must be a positive integer (got {capacity!r})")
+        if device is not None and torch.device(device).type != ws[0].device.type:
+            raise ValueError(f"device {device!r} but the text encoder's weights live on {ws[0].device}")
+        self.pipe, self.hparams, self.stats_dir, self.verbose = pipe, hparams, stats_dir, verbose
+        self.capacity = int(capacity)
+        self._fixed = (lam, e, tuple(hparams.layers), int(getattr(hparams, "num_edit_tokens", 1)))
+        self.keys: Optional[hip.PreservedKeys] = None       # allocated at the first step
+        self.steps = 0
+        self._orig: Optional[Dict[int, torch.Tensor]] = None
+        self._ws: Dict[tuple, hip.PreserveWorkspace] = {}
+
+    @property
+    def preserved(self) -> int:
+        return self.keys.M if self.keys is not None else 0
+
+    def workspace(self, N: int, d: int, h: int, dev) -> "hip.PreserveWorkspace":
+        """(engine side) the workspace of a step of N rows; the two most recent step sizes keep theirs"""
+        key = (N, d, h, str(dev))
+        ws = self._ws.pop(key, None)
+        if ws is None:
+            ws = hip.PreserveWorkspace(N, d, h, self.capacity, dev)
+            while len(self._ws) >= 2:
+                self._ws.pop(next(iter(self._ws)))
+        self._ws[key] = ws
+        return ws
+
+    def _check_step(self, requests, shard):
+        hp = self.hparams
+        now = (float(hp.mom2_update_weight), float(hp.edit_weight), tuple(hp.layers), int(getattr(hp, "num_edit_tokens", 1)))
+        if now != self._fixed:
+            raise ValueError(f"a session's mom2_update_weight, edit_weight, layers and num_edit_tokens are fixed: it was opened with "
+                             f"{self._fixed}, the hparams now say {now}; open a new EditSession")
+        if _shard_from_env(shard).collective:
+            raise NotImplementedError("EditSession runs on one rank: a multi-rank ConceptShard is not supported")
+        forced = edit_engine.SOLVER or os.environ.get("EMCID_SOLVER")
+        if forced in ("direct", "lu"):
+            raise ValueError(f"EMCID_SOLVER={forced} inside a session: the preserved keys live in the dual solver's coordinates")
+        if len(requests) == 0:
+            raise ValueError("a session step needs at least one request")
+        n = len(requests) * self._fixed[3]
+        if self.preserved + n > self.capacity:
+            raise PreservedSetFull(f"{self.preserved} preserved + {n} new concept rows exceed the session's capacity {self.capacity}; "
+                                   f"open a session with a larger capacity (folding a full set into the statistics is not implemented)")
+        return n
+
+    def _weights(self):
+        return {l: nethook.get_parameter(self.pipe.text_encoder, f"{self.hparams.rewrite_module_tmp.format(l)}.weight")
+                for l in self._fixed[2]}
+
+    def apply(self, requests: List[Dict], cache_name: Optional[str] = None, return_orig_text_encoder: bool = False, shard=None,
+              stage1=None):
+        """One step: edit ``requests`` with every earlier step's keys preserved.  Returns what apply_emcid_to_text_encoder does."""
+        n = self._check_step(requests, shard)       # raises before anything is launched or allocated
+        origin_text_encoder = deepcopy(self.pipe.text_encoder) if return_orig_text_encoder else None
+        hp, te = self.hparams, self.pipe.text_encoder
+        weights = self._weights()
+        if self._orig is None:
+            self._orig = {l: w.detach().clone() for l, w in weights.items()}
+        if self.keys is None:
+            w = next(iter(weights.values()))
+            if not w.is_cuda:
+                raise hip.EmcidHipError(f"the text encoder must live in HBM (got {w.device}); there is no CPU path")
+            self.keys = hip.PreservedKeys(len(self._fixed[2]), self.d, self.capacity, w.device)
+        _announce(requests, self.verbose)
+        LP = clip_forward.LAST_PATHS
+        for attempt in (0, 1):
+            plan = prepare_text_encoder_edit(te, self.pipe.tokenizer, requests, hp, hp.layers, hp.mom2_update_weight, self.stats_dir,
+                                             cache_name, "", self.verbose, shard, _default_stage1(self.pipe, hp, stage1))
+            plan.session = self
+            stats_flag = None
+            try:
+                try:
+                    with phase("run + final sync"):
+                        run_encoder_edit(plan, keep_factors=False, restore=False)
+                except BaseException:
+                    plan.restore_weights()
+                    edit_engine._release_workspaces(plan)
+                    raise
+                # (check_info drops a failed plan's own factors: keep their flag word to tell which factorization said no)
+                stats_flag = plan.cov_factors.info if plan.cov_factors is not None else None
+                check_info(plan)                    # restores the weights itself before it raises
+            except clip_forward.StaleWeightCacheError as e:
+                # a weight was rewritten behind the forward's caches: the step is redone once from the live weights, M unchanged
+                if attempt == 1:
+                    raise
+                logging.getLogger("emcid_amd").warning("EditSession.apply: %s; redoing the step from the live weights", e)
+                clip_forward.invalidate_weight_caches(None)
+                LP["stale_cache_retries"] = LP.get("stale_cache_retries", 0) + 1
+                continue
+            except FloatingPointError as e:
+                what = "the statistics lam C' themselves are not positive definite" if stats_flag is not None and int(stats_flag.item()) \
+                    else f"the system of the new keys given the {self.preserved} preserved ones is not positive definite"
+                raise torch.linalg.LinAlgError(
+                    f"session step {self.steps}: {what} ({e}); the edited weights have been restored and nothing was added to "
+                    f"the {self.preserved} preserved rows") from e
+            break
+        self.keys.commit(n)                         # all edited layers together: their rows are already behind row M
+        self.steps += 1
+        LP["session_steps"], LP["session_preserved_rows"] = self.steps, self.keys.M
+        if self.verbose:
+            print(f"Session step {self.steps}: {n} concept rows inserted, {self.keys.M} preserved")
+        return self.pipe, origin_text_encoder
+
+    def reset(self):
+        """Forget the preserved keys; the weights stay as they are, the next step starts a fresh set (M = 0)."""
+        if self.keys is not None:
+            self.keys.reset()
+        self.steps = 0
+        clip_forward.LAST_PATHS["session_steps"] = clip_forward.LAST_PATHS["session_preserved_rows"] = 0
+
+    def restore(self):
+        """The edited weights back at their values of before the session's first step (bit-identical), and the keys forgotten."""
+        if self._orig is not None:
+            with torch.no_grad():
+                for l, w in self._weights().items():
+                    w.copy_(self._orig[l])
+        self.reset()
+
+
 def sweep_emcid_text_encoder(pipe, requests: List[Dict], hparams: EMCIDHyperParams, grid, device: Optional[str] = None,
                              visit=None, cache_name: Optional[str] = None, stat_dir=STATS_DIR, shard=None, stage1=None,
                              verbose: bool = False) -> list:

@@ -27,6 +27,7 @@ EXPORTS = [
     "emcid_edit_dual_stage1_f64", "emcid_edit_dual_pt", "emcid_edit_dual_stage2_f64",
     "emcid_edit_dual_apply_stage1_f64", "emcid_edit_dual_yt", "emcid_edit_dual_apply_stage2_f64",
     "emcid_edit_dual_apply_assemble_f64",
+    "emcid_edit_dual_preserve_workspace_bytes", "emcid_edit_layer_dual_preserve_f64",
     "emcid_edit_lu_workspace_bytes", "emcid_edit_layer_lu_f64", "emcid_lu_solve_f64",
     "emcid_edit_dual_cols_stage1_f64", "emcid_edit_dual_s", "emcid_edit_dual_u", "emcid_edit_dual_cols_stage2_f64",
     "emcid_apply_update2d_f32", "emcid_linear_f32", "emcid_linear_ws_f32", "emcid_linear_workspace_bytes",
@@ -87,6 +88,9 @@ def load():
         "emcid_edit_dual_yt": (p, [p, i64, i64, i64]),
         "emcid_edit_dual_apply_stage2_f64": (i32, [i64, i64, i64, p, i64, i64, i32, i32, p, p, p, p, i64, p, p]),
         "emcid_edit_dual_apply_assemble_f64": (i32, [i64, i64, i64, p, i64, p]),
+        "emcid_edit_dual_preserve_workspace_bytes": (i64, [i64, i64, i64, i64]),
+        "emcid_edit_layer_dual_preserve_f64": (i32, [p, p, p, i64, i64, i64, f64, i32, f64, p, i64, i64, p, i64, p, i64, p, i64, i64,
+                                                     p, p, p, p, p, i64, p, p]),
         "emcid_cholesky_solve_f64": (i32, [p, i64, i64, p, p, p, i64, i64, p]),
         "emcid_edit_dual_cols_stage1_f64": (i32, [p, p, p, i64, i64, i64, f64, i32, f64, p, i64, i64, p, i32, p, i64, p]),
         "emcid_edit_dual_s": (p, [p, i64, i64, i64]),
@@ -1225,3 +1229,76 @@ def edit_layer_dual_apply(K, Zc, zs_t, factors: CovFactors, layer_index: int, ed
                                                 _ptr(ws.buf), ws.nbytes, _ptr(ws.info, torch.int32), _stream(K)),
            "emcid_edit_dual_apply_stage2_f64")
     return {"dW": dW, "ws": ws}
+
+
+class PreservedKeys:
+    """The session state of the dual solver for ``n_layers`` edited layers (include/emcid_hip.h, "PRESERVED key set"): per layer
+    Yp (capacity, dp), Lp (capacity, capacity) and the inverses of Lp's diagonal 128-tiles, f64 in HBM, allocated once —
+    capacity * dp + capacity^2 doubles per layer plus the tiles.  ``M`` rows of every layer are committed; ``edit_layer_dual_preserve``
+    writes a step's rows behind them and ``commit(N)`` makes them count."""
+
+    def __init__(self, n_layers: int, d: int, capacity: int, device):
+        if capacity < 1:
+            raise EmcidHipError(f"the capacity of a preserved key set must be positive (got {capacity})")
+        self.n_layers, self.d, self.capacity, self.M = int(n_layers), int(d), int(capacity), 0
+        self.dp = (d + NB - 1) // NB * NB
+        self.ldl = self.capacity + (self.capacity % 2)
+        tiles = (self.capacity + NB - 1) // NB
+        self.Yp = [torch.zeros(self.capacity, self.dp, dtype=torch.float64, device=device) for _ in range(n_layers)]
+        self.Lp = [torch.zeros(self.capacity, self.ldl, dtype=torch.float64, device=device) for _ in range(n_layers)]
+        self.tile_inv = [torch.zeros(tiles, NB, NB, dtype=torch.float64, device=device) for _ in range(n_layers)]
+
+    def commit(self, N: int):
+        assert self.M + N <= self.capacity
+        self.M += int(N)
+
+    def reset(self):
+        self.M = 0
+
+    @property
+    def nbytes(self) -> int:
+        return sum(t.numel() * 8 for ts in (self.Yp, self.Lp, self.tile_inv) for t in ts)
+
+
+class PreserveWorkspace:
+    """HBM workspace (+ the device `info` word) of emcid_edit_layer_dual_preserve_f64 for steps of N rows at a given capacity."""
+
+    def __init__(self, N: int, d: int, h: int, capacity: int, device):
+        self.key = (N, d, h, capacity)
+        self.nbytes = int(load().emcid_edit_dual_preserve_workspace_bytes(N, d, h, capacity))
+        if self.nbytes <= 0:
+            raise EmcidHipError(f"no preserve workspace for N={N}, d={d}, h={h}, capacity={capacity}")
+        self.buf = torch.zeros(self.nbytes // 8, dtype=torch.float64, device=device)     # zero: the stream-K ticket counters
+        self.info = torch.zeros(1, dtype=torch.int32, device=device)
+
+
+def edit_layer_dual_preserve(K, Zc, zs_t, factors: CovFactors, layer_index: int, edit_weight: float, layers_left: int,
+                             W0, W, state: PreservedKeys, want_dw: bool = True, want_u: bool = False,
+                             ws: Optional[PreserveWorkspace] = None, lam: Optional[float] = None):
+    """``edit_layer_dual_apply`` with the keys of the earlier steps of ``state`` preserved: W = W0 + float(U) for
+    A = lam C' + P^T P + Kt^T Kt.  The step's rows land behind ``state.M`` in layer ``layer_index``'s buffers; nothing is committed
+    here (``state.commit(N)`` after the flag word ``ws.info`` read zero, for all layers together).  Needs the layer's explicit
+    inverse factor.  Returns dict(dW, U (h, d) f64 | None, ws)."""
+    N, d = K.shape
+    h = Zc.shape[1]
+    for t, nm in ((K, "K"), (Zc, "Zc"), (zs_t, "zs_t")) + (((W, "W"), (W0, "W0")) if W is not None else ()):
+        assert t.is_contiguous(), nm
+    assert zs_t.shape == (N, h) and factors.d == d == state.d and (W is None or W.shape == (h, d))
+    if not 0 <= layer_index < state.n_layers:
+        raise EmcidHipError(f"layer index {layer_index} outside the session state's {state.n_layers} layers")
+    if layer_index not in factors.have_inverse:
+        raise EmcidHipError("edit_layer_dual_preserve needs the explicit inverse factor of the layer (cov_inverse)")
+    if state.M + N > state.capacity:
+        raise EmcidHipError(f"{state.M} preserved + {N} new rows exceed the state's capacity {state.capacity}")
+    if ws is None or ws.key != (N, d, h, state.capacity):
+        ws = PreserveWorkspace(N, d, h, state.capacity, K.device)
+    dW = torch.empty(h, d, dtype=torch.float32, device=K.device) if want_dw else None
+    U = torch.empty(h, d, dtype=torch.float64, device=K.device) if want_u else None
+    Yp, Lp, Ti = state.Yp[layer_index], state.Lp[layer_index], state.tile_inv[layer_index]
+    _check(load().emcid_edit_layer_dual_preserve_f64(
+        _ptr(K, torch.float32, "K"), _ptr(Zc, torch.float32, "Zc"), _ptr(zs_t, torch.float32, "zs_t"), N, d, h,
+        float(edit_weight), int(layers_left), factors.lam_ratio(lam), _ptr(factors.buf), factors.n_layers, int(layer_index),
+        _ptr(Yp, torch.float64, "Yp"), Yp.stride(0), _ptr(Lp, torch.float64, "Lp"), Lp.stride(0), _ptr(Ti, torch.float64, "tile_inv"),
+        state.capacity, state.M, _ptr(W0, torch.float32, "W0"), _ptr(W, torch.float32, "W"), _ptr(dW), _ptr(U),
+        _ptr(ws.buf), ws.nbytes, _ptr(ws.info, torch.int32), _stream(K)), "emcid_edit_layer_dual_preserve_f64")
+    return {"dW": dW, "U": U, "ws": ws}

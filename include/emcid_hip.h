@@ -376,6 +376,26 @@ int emcid_edit_dual_apply_stage2_f64(int64_t N, int64_t d, int64_t h, const void
  * latency-bound Cholesky of S starts. */
 int emcid_edit_dual_apply_assemble_f64(int64_t N, int64_t d, int64_t h, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Apply-only dual solver with a PRESERVED key set (edit sessions: a later edit keeps the keys of earlier ones).  The earlier
+ * keys join the preserved second moment, A = lam C' + P^T P + Kt^T Kt (P: the stacked earlier Kt64), without refactoring
+ * lam C': in factor coordinates the state of a layer is
+ *     Yp [M][ldy]      the Yt rows of every earlier step, verbatim (ldy >= d rounded up to 128, even)
+ *     Lp [M][ldl]      lower Cholesky factor of I + Yp Yp^T (ldl >= capacity, even)
+ *     tile_inv         inverses of Lp's 128 x 128 diagonal tiles, ceil(capacity / 128) tiles of 128 x 128 doubles
+ * all three caller-owned, sized for `capacity` rows, 16-byte aligned.  A step with N new rows runs the bordered Cholesky
+ *     B = Yk Yp^T,  Lkp = B Lp^-T,  T = I + Yk Yk^T - Lkp Lkp^T = Lkk Lkk^T,  Zk = T^-1 Rt,  Zp = -Lp^-T (Lkp^T Zk),
+ *     U = (Zk^T Yk + Zp^T Yp) X,  W = W0 + float(U)
+ * (O(N (M + N) d) per step; with M = 0 the algebra of emcid_edit_dual_apply_stage1/2) and writes Yk, [Lkp Lkk] and the
+ * touched tile inverses IN PLACE behind row M: the caller commits the step by passing M + N next time, and must not when
+ * info_dev reports a non-positive pivot of T (rows < M are never written).  Needs X = inv(L) of the layer
+ * (emcid_cov_inverse_f64) and M + N <= capacity.  U_out (optional): U [h][d] f64.  Same scaling arguments as stage 1. */
+int64_t emcid_edit_dual_preserve_workspace_bytes(int64_t N, int64_t d, int64_t h, int64_t capacity);
+int emcid_edit_layer_dual_preserve_f64(const float* K, const float* Zc, const float* zs_t, int64_t N, int64_t d, int64_t h,
+                                       double edit_weight, int layers_left, double lam_ratio, const void* cov_factor_ws,
+                                       int64_t n_layers, int64_t layer_index, double* Yp, int64_t ldy, double* Lp, int64_t ldl,
+                                       double* tile_inv, int64_t capacity, int64_t M, const float* W0, float* W, float* dW_out,
+                                       double* U_out, void* workspace, int64_t workspace_bytes, int* info_dev, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Fallback with the reference's own solver semantics.  torch.linalg.solve (reference: emcid/emcid_main.py:1045-1048) is
  * LAPACK getrf + getrs: LU with partial pivoting, which returns numbers for ANY nonsingular system, whereas the Cholesky
