@@ -2136,6 +2136,109 @@ int emcid_cov_factor_rescale_f64(const void* src_ws, void* dst_ws, int64_t works
     return EMCID_OK;
 }
 
+/* ---- fold a preserved key set into the base factor (edit sessions) -------------------------------------------------------------
+ * A session whose preserved set is full takes its M rows into a factor of its own: with P the stacked (scaled) keys,
+ *     A' = A0 + P^T P,   P = Yp L_s^T,   L_s = sqrt(lam_ratio) L_src   (Yp = P L_s^-T is what the steps kept),
+ * and A' is factored like lam C' itself, so every dual stage runs on it unchanged with M = 0.  `base` carries A0 (and every
+ * earlier fold's P^T P) in fp64 between folds: the SYRK accumulates into it, the factorization consumes a copy.
+ * Both kernels walk the NB x NB tiles on and below the block diagonal, one tile per workgroup, 128 bits per access. */
+__device__ __forceinline__ void lower_tile_of(int t, int& I, int& J) {      // t = I (I + 1) / 2 + J, J <= I
+    I = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
+    while ((I + 1) * (I + 2) / 2 <= t) ++I;
+    while (I * (I + 1) / 2 > t) --I;
+    J = t - I * (I + 1) / 2;
+}
+
+// base = lam * double(fl32(fl32(C * cw) / 0.5f)) inside [0, d)^2, identity on the padding: scale_cov_kernel's values for one layer
+// (the diagonal tiles are filled whole: the SYRK that follows reads and writes whole tiles)
+__global__ __launch_bounds__(256) void fold_base_fill_kernel(const float* __restrict__ C, int d, int dp, double lam, float cw,
+                                                             double* __restrict__ base) {
+    int I, J;
+    lower_tile_of((int)blockIdx.x, I, J);
+    for (int e = threadIdx.x; e < NB * (NB / 2); e += 256) {
+        const int i = I * NB + e / (NB / 2), j = J * NB + 2 * (e % (NB / 2));
+        double2 v;
+        if (i < d) {
+            const float* row = C + (int64_t)i * d;
+            const float c0 = j < d ? row[j] * cw : 0.0f, c1 = j + 1 < d ? row[j + 1] * cw : 0.0f;
+            v.x = j < d ? lam * (double)(c0 / 0.5f) : 0.0;
+            v.y = j + 1 < d ? lam * (double)(c1 / 0.5f) : 0.0;
+        } else {
+            v.x = i == j ? 1.0 : 0.0;
+            v.y = i == j + 1 ? 1.0 : 0.0;
+        }
+        *reinterpret_cast<double2*>(base + (int64_t)i * dp + j) = v;
+    }
+}
+
+// dst = gain * src on the same tiles; lower_only: zeros above the diagonal inside the diagonal tiles (a factor as the
+// factorization leaves it holds no defined values there, and a triangular GEMM hint skips K tiles, not elements)
+__global__ __launch_bounds__(256) void fold_copy_lower_kernel(const double* __restrict__ src, double* __restrict__ dst, int dp,
+                                                              double gain, int lower_only) {
+    int I, J;
+    lower_tile_of((int)blockIdx.x, I, J);
+    for (int e = threadIdx.x; e < NB * (NB / 2); e += 256) {
+        const int i = I * NB + e / (NB / 2), j = J * NB + 2 * (e % (NB / 2));
+        const int64_t at = (int64_t)i * dp + j;
+        double2 v = *reinterpret_cast<const double2*>(src + at);
+        v.x = (lower_only && j > i) ? 0.0 : v.x * gain;
+        v.y = (lower_only && j + 1 > i) ? 0.0 : v.y * gain;
+        *reinterpret_cast<double2*>(dst + at) = v;
+    }
+}
+
+int64_t emcid_cov_factor_fold_workspace_bytes(int64_t M, int64_t d) {
+    if (M <= 0 || d <= 0) return 0;
+    return M * round_up(d, NB) * (int64_t)sizeof(double);          // Q = Yp L_s^T [M, dp]
+}
+
+int emcid_cov_factor_fold_f64(const void* src_ws, double lam_ratio, const double* Yp, int64_t ldy, int64_t M, int64_t capacity,
+                              const float* C, double lam, double edit_weight, int fill_base, void* dst_ws, int64_t n_layers,
+                              int64_t d, int64_t layer_index, double* base, void* workspace, int64_t workspace_bytes,
+                              int* info_dev, void* stream) {
+    EMCID_CHECK_ARG(src_ws && dst_ws && Yp && base && workspace && info_dev && n_layers > 0 && n_layers <= 32 && d > 0 && d <= 32768);
+    EMCID_CHECK_ARG(0 <= layer_index && layer_index < n_layers);
+    EMCID_CHECK_ARG(M > 0 && M <= capacity && capacity < (int64_t)1 << 30);
+    EMCID_CHECK_ARG(lam_ratio > 0.0 && lam_ratio < 1e300);
+    EMCID_CHECK_ARG(src_ws != dst_ws || lam_ratio == 1.0);      // in place: the caller's own workspace, at the caller's own lam
+    EMCID_CHECK_ARG(!fill_base || (C && lam > 0.0 && lam < 1e300 && edit_weight >= 0.0 && edit_weight <= 1.0));
+    const int64_t dp = round_up(d, NB), s_mat = dp * dp, s_inv = inv_doubles(dp), nt = dp / NB;
+    EMCID_CHECK_ARG(aligned16(src_ws) && aligned16(dst_ws) && aligned16(Yp) && aligned16(base) && aligned16(workspace));
+    EMCID_CHECK_ARG(ldy >= dp && ldy % 2 == 0);
+    if (workspace_bytes < emcid_cov_factor_fold_workspace_bytes(M, d))
+        return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small (see emcid_cov_factor_fold_workspace_bytes)");
+    hipStream_t st = (hipStream_t)stream;
+    const double* Lsrc = (const double*)src_ws + (n_layers + layer_index) * s_mat;
+    double* Mb = (double*)dst_ws + layer_index * s_mat;                 // consumed by the factorization; scratch before and after
+    double* Lb = (double*)dst_ws + (n_layers + layer_index) * s_mat;
+    double* Ib = (double*)dst_ws + 2 * n_layers * s_mat + layer_index * s_inv;
+    double* Xb = (double*)dst_ws + n_layers * (2 * s_mat + s_inv) + layer_index * s_mat;
+    double* Q = (double*)workspace;
+    const unsigned n_tri = (unsigned)(nt * (nt + 1) / 2);
+    // the keys back from factor coordinates: Q = Yp L_s^T against a clean lower-triangular copy of L_s in the M region
+    hipLaunchKernelGGL(fold_copy_lower_kernel, dim3(n_tri), dim3(256), 0, st, Lsrc, Mb, (int)dp, sqrt(lam_ratio), 1);
+    {
+        ScopedProf sp(KC_INV_APPLY, st);
+        GemmShape g{Yp, ldy, Mb, dp, (int)M, (int)dp, (int)dp, 0};
+        g.tri = 1;       // B(k, n) = L_s[n][k], zero for k > n
+        g.pair = 1;
+        launch_gemm_f64<true, true>(g, EpiAxpby{Q, dp, 1.0, 0.0}, st, 2);
+    }
+    if (fill_base)
+        hipLaunchKernelGGL(fold_base_fill_kernel, dim3(n_tri), dim3(256), 0, st, C, (int)d, (int)dp, lam, (float)(1.0 - edit_weight),
+                           base);
+    {
+        ScopedProf sp(KC_ASSEMBLE, st);      // base += Q^T Q on the lower tiles: both operands stored [K = M][dp]
+        GemmShape g{Q, dp, Q, dp, (int)dp, (int)dp, (int)M, 1};
+        launch_gemm_f64<false, false>(g, EpiAxpby{base, dp, 1.0, 1.0}, st);
+    }
+    hipLaunchKernelGGL(fold_copy_lower_kernel, dim3(n_tri), dim3(256), 0, st, base, Mb, (int)dp, 1.0, 0);
+    EMCID_TRY(cholesky_serial(Mb, Lb, dp, dp, Ib, info_dev, st, 1, s_mat, s_inv));
+    EMCID_TRY(build_full_inverse(Lb, dp, dp, Ib, Xb, Mb, 1, s_mat, s_inv, st));
+    EMCID_CHECK_LAUNCH();
+    return EMCID_OK;
+}
+
 int64_t emcid_edit_dual_workspace_bytes(int64_t N, int64_t d, int64_t h) {
     if (N <= 0 || d <= 0 || h <= 0) return 0;
     return DualWorkspace(N, d, h).total * (int64_t)sizeof(double);

@@ -578,6 +578,11 @@ def _dual_factors(plan: EncoderEditPlan, form: str, dev):
         # a point of run_sweep: the unit-scale factors of the sweep, rescaled to this point's lam and edit_weight, inverses included
         plan.cov_factors, plan.factors_from_cache = plan.sweep_factors, True
         return None, False
+    private = plan.session.private_factors if plan.session is not None else None
+    if private is not None:
+        # a session that has folded its preserved keys: the factors of lam C' + P^T P, the session's own (emcid_main.EditSession.fold)
+        plan.cov_factors, plan.factors_from_cache = private, True
+        return None, False
     fkey = factor_cache_key([plan.covs[l] for l in plan.layers], plan.lam, plan.edit_weight)
     with ENGINE_LOCK:
         hit = _FACTOR_CACHE.get(fkey) if _factor_cache_size() > 0 and plan.lam > 0 else None

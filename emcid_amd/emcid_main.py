@@ -661,6 +661,8 @@ class EditSession:
         sess = EditSession(pipe, hparams, device, stats_dir=..., capacity=None)
         sess.apply(requests, cache_name=...)      # same mutations / return as apply_emcid_to_text_encoder
         sess.preserved                            # M: preserved concept rows (requests x num_edit_tokens so far)
+        sess.fold()                               # take the M preserved rows into the session's own base factor: M -> 0
+        sess.folded                               # rows folded so far (still preserved, exactly)
         sess.reset()                              # forget the preserved keys (the weights stay as they are)
         sess.restore()                            # the weights of before the first step back, and the keys forgotten
 
@@ -670,15 +672,32 @@ class EditSession:
     step), and a step costs O(N (M + N) d).  All edited layers commit their rows together, after the one flag read at the end
     found every factorization sound; a failed or retried step leaves ``preserved`` where it was.
 
+    A full set is FOLDED instead of dropped: ``fold()`` forms A0' = A0 + P^T P per edited layer (A0 = lam C' at the first fold, the
+    previous fold's system afterwards; P = Yp L^T, the preserved keys back from factor coordinates), factors it once (d^3 / 3 per
+    layer, ``hip.cov_factor_fold``) and goes on with M = 0 on these private factors — every folded key is still preserved exactly,
+    since the system a later step solves is the same sum.  All layers are folded, then ONE pinned flag read decides: zero commits
+    (M -> 0, ``folded`` += M, the session's steps take the private factors from now on), non-zero leaves ``preserved``, the
+    private factors and the weights as they were and raises ``torch.linalg.LinAlgError``.  The private workspace is the
+    session's alone: never put into the engine's factor cache, never handed to plain calls, never rescaled in place; plain
+    calls, sweeps and other sessions keep the cached factors of lam C', which a fold only reads.  ``on_full="fold"`` makes a step
+    that would pass ``capacity`` fold first (``"raise"``, the default: ``PreservedSetFull``).  State cost of a session that has
+    folded, allocated at its first fold: one factored workspace (``emcid_cov_factor_workspace_bytes(n_layers, d)``) plus
+    n_layers x dp^2 doubles of ``base``, the fp64 accumulator of the folded systems (dp = d rounded up to 128); a later fold
+    keeps a copy of both for the time of the fold, so that a refused one leaves them as they were.  ``reset()`` and
+    ``restore()`` drop the private factors and ``base`` and zero ``folded``.
+
     ``device``: as in apply_emcid_to_text_encoder; the state lives on the encoder's own device, ``device`` is only checked against it.
     ``capacity``: the largest M + N (default floor(0.6 d), the engine's dual / direct threshold); a step past it raises
-    ``PreservedSetFull`` before anything is launched.  mom2_update_weight, edit_weight and layers are fixed at construction
+    ``PreservedSetFull`` before anything is launched (with ``on_full="fold"``: only a step that exceeds it by itself).
+    mom2_update_weight, edit_weight and layers are fixed at construction
     (``hparams`` may be mutated afterwards, a step then refuses).  Not run by a session: several ranks (a collective
     ``ConceptShard``), SDXL, cross-attention edits, EMCID_SOLVER=direct|lu; there is no pivoted-LU fallback either — a
     non-positive pivot restores the weights and raises ``torch.linalg.LinAlgError``."""
 
     def __init__(self, pipe, hparams: EMCIDHyperParams, device: Optional[str] = None, stats_dir=STATS_DIR,
-                 capacity: Optional[int] = None, verbose: bool = False):
+                 capacity: Optional[int] = None, verbose: bool = False, on_full: str = "raise"):
+        if on_full not in ("raise", "fold"):
+            raise ValueError(f"on_full must be 'raise' or 'fold' (got {on_full!r})")
         if isinstance(hparams, EMCIDXLHyperParams) or getattr(pipe, "text_encoder_2", None) is not None:
             raise NotImplementedError("EditSession edits one CLIP text encoder: the SDXL pair (EMCIDXLHyperParams / text_encoder_2) "
                                       "is not supported")
@@ -708,16 +727,66 @@ class EditSession:
         if device is not None and torch.device(device).type != ws[0].device.type:
             raise ValueError(f"device {device!r} but the text encoder's weights live on {ws[0].device}")
         self.pipe, self.hparams, self.stats_dir, self.verbose = pipe, hparams, stats_dir, verbose
-        self.capacity = int(capacity)
+        self.capacity, self.on_full = int(capacity), on_full
         self._fixed = (lam, e, tuple(hparams.layers), int(getattr(hparams, "num_edit_tokens", 1)))
         self.keys: Optional[hip.PreservedKeys] = None       # allocated at the first step
         self.steps = 0
         self._orig: Optional[Dict[int, torch.Tensor]] = None
         self._ws: Dict[tuple, hip.PreserveWorkspace] = {}
+        self.folded, self.folds = 0, 0                       # rows taken into the private base factor, and how often
+        self.private_factors: Optional[hip.CovFactors] = None    # the factors of lam C' + (folded P)^T P: this session's steps only
+        self._base: Optional[torch.Tensor] = None            # (n_layers, dp, dp) f64: the folded systems themselves
+        self._shared = None     # (factors, covs) of the last sound step: what the preserved rows' coordinates refer to
 
     @property
     def preserved(self) -> int:
         return self.keys.M if self.keys is not None else 0
+
+    def fold(self):
+        """Take the ``preserved`` rows of every edited layer into the session's private base factor and go on with M = 0; the
+        folded keys stay preserved exactly.  A no-op without preserved rows.  One flag read; a non-positive pivot leaves
+        ``preserved``, ``folded``, the private factors and the weights as they were and raises ``torch.linalg.LinAlgError``."""
+        M = self.preserved
+        if M == 0:
+            return
+        dev = self.keys.Yp[0].device
+        if not self.keys.Yp[0].is_cuda or self._shared is None:
+            raise hip.EmcidHipError(f"a fold runs on the factors of the session's last step in HBM (state on {dev}); there is no CPU path")
+        lam, e, layers, _ = self._fixed
+        first = self.private_factors is None
+        src = self._shared[0] if first else self.private_factors
+        if first:
+            dst = hip.CovFactors(len(layers), self.d, dev)
+            base = torch.empty(len(layers), dst.dp, dst.dp, dtype=torch.float64, device=dev)
+            keep = None
+        else:
+            dst, base = src, self._base
+            keep = (dst.buf.clone(), base.clone())          # (a refused fold puts both back)
+        dst.info.zero_()
+        ws = torch.empty(M * dst.dp, dtype=torch.float64, device=dev)
+        for i in range(len(layers)):
+            hip.cov_factor_fold(src, self.keys, i, self._shared[1][i] if first else None, lam, e, dst, base, ws=ws)
+        flag = torch.empty(1, dtype=torch.int32, pin_memory=True)
+        flag.copy_(dst.info, non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+        code = int(flag.item())
+        if code != 0:
+            if keep is not None:
+                dst.buf.copy_(keep[0])
+                base.copy_(keep[1])
+                dst.info.zero_()
+            raise torch.linalg.LinAlgError(
+                f"fold after step {self.steps}: lam C' plus the {self.folded} folded and {M} preserved keys is not positive definite "
+                f"(non-positive pivot at column {code - 1}): check the statistics; the {M} preserved rows, the private factors and "
+                f"the weights are as they were")
+        self.private_factors, self._base = dst, base
+        self.keys.reset()
+        self.folded += M
+        self.folds += 1
+        LP = clip_forward.LAST_PATHS
+        LP["session_folds"], LP["session_folded_rows"], LP["session_preserved_rows"] = self.folds, self.folded, 0
+        if self.verbose:
+            print(f"Session fold {self.folds}: {M} preserved rows folded into the base factor, {self.folded} folded so far")
 
     def workspace(self, N: int, d: int, h: int, dev) -> "hip.PreserveWorkspace":
         """(engine side) the workspace of a step of N rows; the two most recent step sizes keep theirs"""
@@ -744,9 +813,12 @@ class EditSession:
         if len(requests) == 0:
             raise ValueError("a session step needs at least one request")
         n = len(requests) * self._fixed[3]
+        if self.preserved + n > self.capacity and self.on_full == "fold" and n <= self.capacity:
+            return n                                # apply() folds first
         if self.preserved + n > self.capacity:
             raise PreservedSetFull(f"{self.preserved} preserved + {n} new concept rows exceed the session's capacity {self.capacity}; "
-                                   f"open a session with a larger capacity (folding a full set into the statistics is not implemented)")
+                                   f"open a session with a larger capacity, or with on_full='fold' (sess.fold() takes a full set into "
+                                   f"the session's base factor)")
         return n
 
     def _weights(self):
@@ -757,6 +829,8 @@ class EditSession:
               stage1=None):
         """One step: edit ``requests`` with every earlier step's keys preserved.  Returns what apply_emcid_to_text_encoder does."""
         n = self._check_step(requests, shard)       # raises before anything is launched or allocated
+        if self.preserved + n > self.capacity:      # (on_full="fold": the step fits once the preserved rows are folded)
+            self.fold()
         origin_text_encoder = deepcopy(self.pipe.text_encoder) if return_orig_text_encoder else None
         hp, te = self.hparams, self.pipe.text_encoder
         weights = self._weights()
@@ -802,7 +876,10 @@ class EditSession:
             break
         self.keys.commit(n)                         # all edited layers together: their rows are already behind row M
         self.steps += 1
+        if self.private_factors is None:            # the workspace this step's rows are coordinates of, and its statistics
+            self._shared = (plan.cov_factors, [plan.covs[l] for l in plan.layers])
         LP["session_steps"], LP["session_preserved_rows"] = self.steps, self.keys.M
+        LP["session_folds"], LP["session_folded_rows"] = self.folds, self.folded
         if self.verbose:
             print(f"Session step {self.steps}: {n} concept rows inserted, {self.keys.M} preserved")
         return self.pipe, origin_text_encoder
@@ -812,7 +889,10 @@ class EditSession:
         if self.keys is not None:
             self.keys.reset()
         self.steps = 0
-        clip_forward.LAST_PATHS["session_steps"] = clip_forward.LAST_PATHS["session_preserved_rows"] = 0
+        self.private_factors = self._base = self._shared = None
+        self.folded = self.folds = 0
+        LP = clip_forward.LAST_PATHS
+        LP["session_steps"] = LP["session_preserved_rows"] = LP["session_folds"] = LP["session_folded_rows"] = 0
 
     def restore(self):
         """The edited weights back at their values of before the session's first step (bit-identical), and the keys forgotten."""

@@ -28,6 +28,7 @@ EXPORTS = [
     "emcid_edit_dual_apply_stage1_f64", "emcid_edit_dual_yt", "emcid_edit_dual_apply_stage2_f64",
     "emcid_edit_dual_apply_assemble_f64",
     "emcid_edit_dual_preserve_workspace_bytes", "emcid_edit_layer_dual_preserve_f64",
+    "emcid_cov_factor_fold_workspace_bytes", "emcid_cov_factor_fold_f64",
     "emcid_edit_lu_workspace_bytes", "emcid_edit_layer_lu_f64", "emcid_lu_solve_f64",
     "emcid_edit_dual_cols_stage1_f64", "emcid_edit_dual_s", "emcid_edit_dual_u", "emcid_edit_dual_cols_stage2_f64",
     "emcid_apply_update2d_f32", "emcid_linear_f32", "emcid_linear_ws_f32", "emcid_linear_workspace_bytes",
@@ -38,7 +39,7 @@ EXPORTS = [
 PROF_CLASSES = ["prep", "assemble", "chol_leaf", "chol_panel", "chol_trail", "trsm_diag", "trsm_update", "delta_w",
                 "gram", "gather", "dgemm", "misc", "inv_build", "chol_inner", "inv_apply", "inv_block", "linear"]
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 NB = 128      # Cholesky block (csrc/common.h)
 NPAD = 64     # concept padding of the f64 stacks (csrc/common.h)
 
@@ -91,6 +92,8 @@ def load():
         "emcid_edit_dual_preserve_workspace_bytes": (i64, [i64, i64, i64, i64]),
         "emcid_edit_layer_dual_preserve_f64": (i32, [p, p, p, i64, i64, i64, f64, i32, f64, p, i64, i64, p, i64, p, i64, p, i64, i64,
                                                      p, p, p, p, p, i64, p, p]),
+        "emcid_cov_factor_fold_workspace_bytes": (i64, [i64, i64]),
+        "emcid_cov_factor_fold_f64": (i32, [p, f64, p, i64, i64, i64, p, f64, f64, i32, p, i64, i64, i64, p, p, i64, p, p]),
         "emcid_cholesky_solve_f64": (i32, [p, i64, i64, p, p, p, i64, i64, p]),
         "emcid_edit_dual_cols_stage1_f64": (i32, [p, p, p, i64, i64, i64, f64, i32, f64, p, i64, i64, p, i32, p, i64, p]),
         "emcid_edit_dual_s": (p, [p, i64, i64, i64]),
@@ -1302,3 +1305,45 @@ def edit_layer_dual_preserve(K, Zc, zs_t, factors: CovFactors, layer_index: int,
         state.capacity, state.M, _ptr(W0, torch.float32, "W0"), _ptr(W, torch.float32, "W"), _ptr(dW), _ptr(U),
         _ptr(ws.buf), ws.nbytes, _ptr(ws.info, torch.int32), _stream(K)), "emcid_edit_layer_dual_preserve_f64")
     return {"dW": dW, "U": U, "ws": ws}
+
+
+def cov_factor_fold(src: CovFactors, state: PreservedKeys, layer_index: int, cov: Optional[torch.Tensor], lam: float,
+                    edit_weight: float, dst: CovFactors, base: torch.Tensor, ws: Optional[torch.Tensor] = None) -> CovFactors:
+    """Fold the ``state.M`` preserved rows of layer ``layer_index`` into the caller's own factors (include/emcid_hip.h,
+    emcid_cov_factor_fold_f64): ``base`` (n_layers, dp, dp) f64 += P^T P for the keys P = Yp L_s^T that ``state`` holds in the
+    coordinates of ``src`` (lam: the session's own, any ratio to ``src.lam``), then layer ``layer_index`` of ``dst`` = the factor
+    of ``base``, its block inverses and X = inv(L).  ``cov`` (d, d) fp32: the layer's statistics, from which ``base`` is filled
+    first (the first fold); ``None``: ``base`` is what the previous fold left.  ``src`` is only read; ``dst is src`` folds the
+    caller's own workspace in place (``src.lam`` must be ``lam`` then).  ``ws``: an f64 scratch tensor of at least
+    ``state.M * dp`` elements.  Asynchronous on the current stream; ``dst.info`` reports a non-positive pivot.  Returns ``dst``
+    with ``lam`` / ``edit_weight`` recorded, ``have_inverse`` updated and ``cached = False``; ``state`` is not touched."""
+    lib = load()
+    if src.n_layers != dst.n_layers or src.d != dst.d or state.d != src.d:
+        raise EmcidHipError(f"fold: src ({src.n_layers} x {src.d}), dst ({dst.n_layers} x {dst.d}) and the state (d = {state.d}) "
+                            f"must describe the same layers")
+    if dst is not src and dst.cached:
+        raise EmcidHipError("fold: dst is a workspace of the factor cache; a fold writes only into a workspace its caller owns")
+    if dst is src and src.cached:
+        raise EmcidHipError("fold: an in-place fold needs a workspace its caller owns (this one belongs to the factor cache)")
+    dp = src.dp
+    if base.dtype != torch.float64 or not base.is_contiguous() or base.numel() != src.n_layers * dp * dp:
+        raise EmcidHipError(f"fold: base must be a contiguous f64 tensor of {src.n_layers} x {dp} x {dp}")
+    if cov is not None:
+        assert cov.shape == (src.d, src.d) and cov.is_contiguous()
+    M = int(state.M)
+    need = int(lib.emcid_cov_factor_fold_workspace_bytes(max(M, 1), src.d))
+    if ws is None:
+        ws = torch.empty(need // 8, dtype=torch.float64, device=src.buf.device)
+    if src.ready is not None:
+        torch.cuda.current_stream(src.buf.device).wait_event(src.ready)
+    in_range = 0 <= layer_index < state.n_layers
+    Yp = state.Yp[layer_index if in_range else 0]
+    base_l = base.view(src.n_layers, dp, dp)[layer_index if in_range else 0]
+    _check(lib.emcid_cov_factor_fold_f64(
+        _ptr(src.buf), src.lam_ratio(lam), _ptr(Yp, torch.float64, "Yp"), Yp.stride(0), M, state.capacity,
+        _ptr(cov, torch.float32, "C"), float(lam), float(edit_weight), int(cov is not None), _ptr(dst.buf), src.n_layers, src.d,
+        int(layer_index), _ptr(base_l, torch.float64, "base"), _ptr(ws, torch.float64, "ws"), ws.numel() * 8,
+        _ptr(dst.info, torch.int32), _stream(src.buf)), "emcid_cov_factor_fold_f64")
+    dst.have_inverse.add(int(layer_index))
+    dst.lam, dst.edit_weight, dst.cached = float(lam), float(edit_weight), False
+    return dst

@@ -28,7 +28,7 @@ extern "C" {
 #define EMCID_ERR_HIP (-2)
 #define EMCID_ERR_WORKSPACE (-3)
 
-#define EMCID_ABI_VERSION 15
+#define EMCID_ABI_VERSION 16
 
 /* ABI version of the loaded library (host-only, no GPU needed). */
 int emcid_abi_version(void);
@@ -395,6 +395,24 @@ int emcid_edit_layer_dual_preserve_f64(const float* K, const float* Zc, const fl
                                        int64_t n_layers, int64_t layer_index, double* Yp, int64_t ldy, double* Lp, int64_t ldl,
                                        double* tile_inv, int64_t capacity, int64_t M, const float* W0, float* W, float* dW_out,
                                        double* U_out, void* workspace, int64_t workspace_bytes, int* info_dev, void* stream);
+
+/* Fold a preserved key set into a base factor the caller owns (ABI 16; edit sessions whose set is full).  For ONE layer:
+ *     Q = Yp L_s^T,  L_s = sqrt(lam_ratio) L_src    the M preserved (scaled) keys back from factor coordinates; lam_ratio = the
+ *                                                    caller's lam / the lam src_ws was factored with, exact for any ratio
+ *     base += Q^T Q                                  fp64 [dp][dp] accumulator of the layer's system at the caller's own lam, lower
+ *                                                    128 x 128 tiles; with fill_base it is first set from the fp32 statistics C [d][d]
+ *                                                    exactly as emcid_factor_cov_f64 sets lam C' (identity on the padding to dp)
+ *     L' L'^T = base, the block inverses, X' = L'^-1 into layer `layer_index` of dst_ws, in the layout every dual stage reads
+ * so the stages run on dst_ws with M = 0 and lam_ratio = 1 while every folded key stays preserved exactly.  src_ws is only read
+ * (it may be a workspace other edits share); src_ws == dst_ws is allowed with lam_ratio == 1 (a later fold of the caller's own
+ * workspace).  Both workspaces have the same (n_layers, d); the other layers of dst_ws are not touched.  Yp as in
+ * emcid_edit_layer_dual_preserve_f64, 0 < M <= capacity; workspace: emcid_cov_factor_fold_workspace_bytes(M, d).  No host
+ * synchronisation; info_dev reports a non-positive pivot like emcid_factor_cov_f64 (base then holds the sum all the same). */
+int64_t emcid_cov_factor_fold_workspace_bytes(int64_t M, int64_t d);
+int emcid_cov_factor_fold_f64(const void* src_ws, double lam_ratio, const double* Yp, int64_t ldy, int64_t M, int64_t capacity,
+                              const float* C, double lam, double edit_weight, int fill_base, void* dst_ws, int64_t n_layers,
+                              int64_t d, int64_t layer_index, double* base, void* workspace, int64_t workspace_bytes,
+                              int* info_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Fallback with the reference's own solver semantics.  torch.linalg.solve (reference: emcid/emcid_main.py:1045-1048) is
