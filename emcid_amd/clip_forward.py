@@ -43,10 +43,11 @@ SPLIT_GEMM = os.environ.get("EMCID_SPLIT_GEMM", "1") != "0"
 # trie forwards that had to FALL BACK to the hooked HF encoder (each one is also logged once per reason).  sweep_*: gauges of the
 # last sweep_emcid_text_encoder (edit_engine.run_sweep): its points, the covariance factorizations it ran, its prefix runs.
 # session_*: gauges of the last EditSession step (emcid_main.EditSession): its steps so far and preserved concept rows; its folds
-# and the rows they took into the session's base factor.
+# and the rows they took into the session's base factor; the rows its retain lists added (EditSession.retain), folded ones included.
 LAST_PATHS = {"linear_sp16": 0, "linear_f32": 0, "linear_torch": 0, "native_layers": 0, "fused_edit_layers": 0, "forward_trie": 0,
               "forward_hf": 0, "forward_hf_fallback": 0, "sweep_points": 0, "sweep_cov_factorizations": 0, "sweep_prefix_runs": 0,
-              "session_steps": 0, "session_preserved_rows": 0, "session_folds": 0, "session_folded_rows": 0}
+              "session_steps": 0, "session_preserved_rows": 0, "session_folds": 0, "session_folded_rows": 0,
+              "session_retained_rows": 0}
 _FALLBACK_SEEN = set()
 
 

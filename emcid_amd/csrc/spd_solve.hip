@@ -64,6 +64,46 @@ __global__ __launch_bounds__(256) void prep_kr_kernel(const float* __restrict__ 
     }
 }
 
+// Kt64[n][j] = double(K[n][j]) * s * g alone (zero padded to [Np][dp]): a retained key (emcid_session_retain_f64) has no
+// residual side; the conversion is prep_kr_kernel's, operation for operation
+__global__ __launch_bounds__(256) void prep_k_kernel(const float* __restrict__ K, int N, int d, double s, double* __restrict__ Kt64,
+                                                      int dp, double g) {
+    const int n = blockIdx.x;
+    for (int j = threadIdx.x; j < dp; j += 256) {
+        double v = 0.0;
+        if (n < N && j < d) v = (double)K[(int64_t)n * d + j] * s * g;
+        Kt64[(int64_t)n * dp + j] = v;
+    }
+}
+
+// The readout of a preserve step (emcid_session_step_norms_f64): one wave per output, four outputs per workgroup.
+//   o <  M              drift[o]        = || ZT[0:h, o] ||_2          (ZT = [Zp^T | Zk^T] [h][ldz]: column o, strided by ldz)
+//   M <= o < M + N      left[o - M]     = || ZT[0:h, o] ||_2
+//   M + N <= o          resid[o - M - N] = || Rt[o - M - N, 0:h] ||_2  (Rt [N][ldr])
+__global__ __launch_bounds__(256) void step_norms_kernel(const double* __restrict__ ZT, int64_t ldz, const double* __restrict__ Rt,
+                                                          int64_t ldr, int h, int M, int N, double* __restrict__ drift,
+                                                          double* __restrict__ left, double* __restrict__ resid) {
+    const int lane = threadIdx.x & 63;
+    const int o = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (o >= M + 2 * N) return;       // (whole waves leave: no lane of a wave that stays is missing from the shuffles)
+    double s = 0.0;
+    if (o < M + N) {
+        for (int i = lane; i < h; i += 64) {
+            const double v = ZT[(int64_t)i * ldz + o];
+            s += v * v;
+        }
+    } else {
+        const double* r = Rt + (int64_t)(o - M - N) * ldr;
+        for (int i = lane; i < h; i += 64) s += r[i] * r[i];
+    }
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
+    if (lane == 0) {
+        if (o < M) drift[o] = sqrt(s);
+        else if (o < M + N) left[o - M] = sqrt(s);
+        else resid[o - M - N] = sqrt(s);
+    }
+}
+
 __global__ __launch_bounds__(256) void copy2d_f64_kernel(const double* __restrict__ src, int64_t lds_, double* __restrict__ dst,
                                                           int64_t ldd, int rows, int cols, double scale = 1.0) {
     const int r = blockIdx.x;
@@ -1749,6 +1789,28 @@ struct PreserveWorkspace {
     }
 };
 
+// workspace of emcid_session_retain_f64: the key half of a PreserveWorkspace (no Rt, RT, Y2, V, U, ZT, G)
+struct RetainWorkspace {
+    int64_t Np, dp, cp;
+    int64_t off_K, off_Y, off_S, off_LS, off_invS, off_SK, off_XT, off_TT, off_B, total;   // doubles
+    RetainWorkspace(int64_t N, int64_t d, int64_t capacity) {
+        Np = round_up(N, NB);
+        dp = round_up(d, NB);
+        cp = round_up(capacity, NB);
+        int64_t o = 0;
+        off_K = o; o += Np * dp;
+        off_Y = o; o += Np * dp;
+        off_S = o; o += Np * Np;
+        off_LS = o; o += Np * Np;
+        off_invS = o; o += inv_doubles(Np);
+        off_SK = o; o += streamk_workspace_doubles(kStreamKWgs);
+        off_XT = o; o += Np * Np;
+        off_TT = o; o += Np * NB;
+        off_B = o; o += Np * cp;
+        total = o;
+    }
+};
+
 }  // namespace emcid
 
 using namespace emcid;
@@ -2598,6 +2660,82 @@ int emcid_edit_layer_dual_preserve_f64(const float* K, const float* Zc, const fl
     apply_inverse_backward(cov_inverse(cov_factor_ws, n_layers, dp, layer_index), dp, V, (int)h, (int)dp, U, dp, st, base + ws.off_SK);
     if (W || dW_out) hipLaunchKernelGGL(apply_u2d_kernel, dim3((unsigned)h), dim3(256), 0, st, U, dp, W0, W, dW_out, (int)d);
     if (U_out) hipLaunchKernelGGL(copy2d_f64_kernel, dim3((unsigned)h), dim3(256), 0, st, U, dp, U_out, d, (int)h, (int)d, 1.0);
+    EMCID_CHECK_LAUNCH();
+    return EMCID_OK;
+}
+
+/* ---- edit sessions: a RETAIN list — preserved rows with a zero residual -------------------------------------------------------
+ * The first half of emcid_edit_layer_dual_preserve_f64 for keys that are to stay where they are: Yk, B, Lkp, T, its Cholesky and
+ * the append behind row M.  With Rt = 0 the step's Zk, Zp and U vanish identically, so that half is not run at all: no Zc, no
+ * targets, no weights. */
+int64_t emcid_session_retain_workspace_bytes(int64_t N, int64_t d, int64_t capacity) {
+    if (N <= 0 || d <= 0 || capacity < N) return 0;
+    return RetainWorkspace(N, d, capacity).total * (int64_t)sizeof(double);
+}
+
+int emcid_session_retain_f64(const float* K, int64_t N, int64_t d, double row_scale, double lam_ratio, const void* cov_factor_ws,
+                             int64_t n_layers, int64_t layer_index, double* Yp, int64_t ldy, double* Lp, int64_t ldl,
+                             double* tile_inv, int64_t capacity, int64_t M, void* workspace, int64_t workspace_bytes, int* info_dev,
+                             void* stream) {
+    EMCID_CHECK_ARG(K && N > 0 && d > 0 && Yp && Lp && tile_inv && workspace && info_dev && cov_factor_ws);
+    EMCID_CHECK_ARG(0 <= layer_index && layer_index < n_layers && row_scale > 0.0 && row_scale < 1e150);
+    EMCID_CHECK_ARG(lam_ratio > 0.0 && lam_ratio < 1e300);
+    EMCID_CHECK_ARG(M >= 0 && M + N <= capacity && capacity < (int64_t)1 << 30);
+    RetainWorkspace ws(N, d, capacity);
+    EMCID_CHECK_ARG(ldy >= ws.dp && ldy % 2 == 0 && ldl >= capacity && ldl % 2 == 0 && aligned16(Yp) && aligned16(Lp) && aligned16(tile_inv));
+    if (workspace_bytes < ws.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    double* base = (double*)workspace;
+    double *Kt = base + ws.off_K, *Yt = base + ws.off_Y, *S = base + ws.off_S, *LS = base + ws.off_LS, *invS = base + ws.off_invS;
+    double *XT = base + ws.off_XT, *TT = base + ws.off_TT, *Bw = base + ws.off_B;
+    const int64_t dp = ws.dp, Np = ws.Np, cp = ws.cp;
+    {
+        ScopedProf sp(KC_PREP, st);
+        hipLaunchKernelGGL(prep_k_kernel, dim3((unsigned)Np), dim3(256), 0, st, K, (int)N, (int)d, row_scale, Kt, (int)dp,
+                           1.0 / sqrt(lam_ratio));
+    }
+    // Yt = Kt64 X^T over the Np padded rows, as stage 1 of the apply-only form runs the whole concept range
+    apply_inverse_forward(cov_inverse(cov_factor_ws, n_layers, dp, layer_index), dp, Kt, Yt, (int)Np, st, base + ws.off_SK);
+    double* Yk = Yp + M * ldy;
+    double* Lkp = Lp + M * ldl;
+    hipLaunchKernelGGL(copy2d_f64_kernel, dim3((unsigned)N), dim3(256), 0, st, Yt, dp, Yk, ldy, (int)N, (int)dp, 1.0);
+    if (M > 0) {
+        hipLaunchKernelGGL(zero2d_f64_kernel, dim3((unsigned)N, 1u), dim3(256), 0, st, Bw, cp, (int64_t)0, (int)M);
+        {
+            ScopedProf sp(KC_ASSEMBLE, st);      // B = Yk Yp^T
+            GemmShape g{Yk, ldy, Yp, ldy, (int)N, (int)M, (int)dp, 0};
+            launch_gemm_f64<true, true>(g, EpiAxpby{Bw, cp, 1.0, 1.0}, st);
+        }
+        trsm_tiles_forward(Lp, ldl, tile_inv, M, Bw, cp, Lkp, ldl, (int)N, st);
+    }
+    assemble_schur_system(Yk, ldy, dp, Lkp, ldl, M, S, (int)N, (int)Np, st);
+    // (the factorization's launches are those of a preserve step, the explicit inverse of LS riding in them included)
+    const bool xrow = cholesky_takes_shadow(Np);
+    const XrowJob xj{XT, Np, TT};
+    EMCID_TRY(cholesky_impl(S, LS, Np, Np, invS, info_dev, st, nullptr, xrow ? &xj : nullptr));
+    hipLaunchKernelGGL(append_factor_kernel, dim3((unsigned)N), dim3(256), 0, st, LS, Np, Lp, ldl, (int)M, (int)N);
+    {
+        ScopedProf sp(KC_INV_BLOCK, st);
+        const unsigned tiles = (unsigned)((M + N - 1) / NB - M / NB + 1);
+        hipLaunchKernelGGL(tile_inverse_extend_kernel, dim3(tiles, NB / 16), dim3(64), 0, st, Lp, ldl, tile_inv, (int)M, (int)(M + N));
+    }
+    EMCID_CHECK_LAUNCH();
+    return EMCID_OK;
+}
+
+/* The readout of the preserve step that has just run on `workspace` (same N, d, h, capacity, M, same stream): the step left
+ * ZT = [Zp^T | Zk^T] [h][M + N] and Rt [N][h] there.  One launch. */
+int emcid_session_step_norms_f64(const void* workspace, int64_t workspace_bytes, int64_t N, int64_t d, int64_t h, int64_t capacity,
+                                 int64_t M, double* drift_out, double* left_out, double* resid_out, void* stream) {
+    EMCID_CHECK_ARG(workspace && N > 0 && d > 0 && h > 0 && left_out && resid_out && (drift_out || M == 0));
+    EMCID_CHECK_ARG(M >= 0 && M + N <= capacity && capacity < (int64_t)1 << 30);
+    PreserveWorkspace pw(N, d, h, capacity);
+    if (workspace_bytes < pw.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
+    const double* base = (const double*)workspace;
+    const double *R = base + pw.dual.off_R, *ZT = base + pw.off_ZT;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(step_norms_kernel, dim3((unsigned)((M + 2 * N + 3) / 4)), dim3(256), 0, st, ZT, pw.cp, R, pw.dual.hp, (int)h,
+                       (int)M, (int)N, drift_out, left_out, resid_out);
     EMCID_CHECK_LAUNCH();
     return EMCID_OK;
 }

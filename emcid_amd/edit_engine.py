@@ -19,6 +19,7 @@ Same K, Zc, A, X, R, dW as the reference's loop (same inputs to every step), 1 p
 touches only HBM-resident inputs — that is the region bench.py times.
 """
 import logging
+import math
 import os
 import threading
 import time
@@ -142,6 +143,7 @@ class EncoderEditPlan:
     num_edit_tokens: int = 1             # k > 1: k key / value rows per request (last subject token, EOS, padding), n_total = N k
     sweep_factors: Optional[hip.CovFactors] = None       # set by run_sweep: the point's rescaled factors, used as they are
     session: object = None               # set by emcid_main.EditSession: the preserved keys (``.keys``: hip.PreservedKeys) of the earlier steps
+    retain_weight: Optional[float] = None    # set by EditSession.retain: the pass only ENTERS its keys into the session's set (no targets, no weight written)
 
     def weight_name(self, layer):
         return f"{self.rewrite_module_tmp.format(layer)}.weight"
@@ -675,8 +677,8 @@ def run_encoder_edit(plan: EncoderEditPlan, keep_factors: bool = False, trace: b
     plan.factor_key, plan.factors_from_cache = None, False
     if form in DUAL_FORMS:
         # (a session brings its own workspace, sized by its capacity)
-        plan.dual_ws = plan.session.workspace(plan.n_total, d, h, dev) if form == "dual_preserve" \
-            else _workspace("dual", plan.n_total, d, h, dev, plan)
+        plan.dual_ws = plan.session.workspace(plan.n_total, d, h, dev, retain=plan.retain_weight is not None) \
+            if form == "dual_preserve" else _workspace("dual", plan.n_total, d, h, dev, plan)
         plan.dual_ws.info.zero_()
         fac_done, lazy = _dual_factors(plan, form, dev)
     else:
@@ -688,6 +690,15 @@ def run_encoder_edit(plan: EncoderEditPlan, keep_factors: bool = False, trace: b
     def solve(i, layer, K_local, Zc_local):
         """All-gather the shard's K/Zc rows, run the closed form, leave W0 + dW in the live weight.  ``Zc_local`` may be
         a callable K -> Zc (fc2 applied to the gathered keys): then only K crosses the links."""
+        if plan.retain_weight is not None:
+            # a retain list (EditSession.retain): the keys enter the session's preserved set with a zero residual — no Zc, no targets,
+            # and the layer's weight is neither read by the solver nor written, so the forward goes on with it as it is
+            if fac_done is not None:
+                torch.cuda.current_stream(dev).wait_event(fac_done[i])
+            hip.session_retain(K_local, plan.cov_factors, i, math.sqrt(plan.retain_weight * plan.edit_weight / 0.5), plan.session.keys,
+                               ws=plan.dual_ws, lam=plan.lam)
+            edits.append(LayerEdit(layer, plan.weight_name(layer), None, None, None, K_local if trace else None, None))
+            return
         try:
             with _dist_phase("solve (incl. its collectives)", dev):
                 K = _all_gather_rows(K_local, plan)
@@ -733,6 +744,8 @@ def run_encoder_edit(plan: EncoderEditPlan, keep_factors: bool = False, trace: b
             # for all layers at once after check_info
             res = hip.edit_layer_dual_preserve(K, Zc, plan.zs_t, plan.cov_factors, i, plan.edit_weight, L - i, W0, W,
                                                plan.session.keys, ws=plan.dual_ws, lam=plan.lam)
+            if plan.session.report_on:      # the step's readout, from what it left in its workspace: one more launch per layer
+                hip.session_step_norms(plan.dual_ws, K.shape[0], d, h, plan.session.keys, out=plan.session.report_row(i, K.shape[0]))
             return res["dW"], None, None
         if form == "dual":
             sharded = plan.shard.collective
@@ -840,7 +853,8 @@ def run_encoder_edit(plan: EncoderEditPlan, keep_factors: bool = False, trace: b
         def make_hook(i, layer):
             def hook(mod, inputs, output):
                 x = inputs[0]
-                solve(i, layer, gather_request_means(x, plan.ensure_batch()), gather_request_means(output, plan.ensure_batch()))
+                solve(i, layer, gather_request_means(x, plan.ensure_batch()),
+                      None if plan.retain_weight is not None else gather_request_means(output, plan.ensure_batch()))
                 if layer == last:
                     raise StopForward()
                 return clip_forward.linear(x.reshape(-1, x.shape[-1]), mod.weight, mod.bias).reshape(*x.shape[:-1], -1) \

@@ -505,8 +505,9 @@ class _LazyVstars:
 
 
 def prepare_text_encoder_edit(text_encoder, tokenizer, requests, hparams, layers, lam, stat_dir, cache_name,
-                              suffix="", verbose=True, shard=None, stage1=None) -> EncoderEditPlan:
-    """Host side of one encoder's edit: v* rows, C per layer (HBM-resident), tokenized prompts + lookup."""
+                              suffix="", verbose=True, shard=None, stage1=None, with_targets=True) -> EncoderEditPlan:
+    """Host side of one encoder's edit: v* rows, C per layer (HBM-resident), tokenized prompts + lookup.  ``with_targets=False``
+    (a session's retain list): no v* is looked up, read or computed, ``cache_name`` and ``stage1`` are not touched."""
     w = None
     for layer in layers:   # resolve every edited weight now: LookupError before any GPU work, like the reference (:858-863)
         w = nethook.get_parameter(text_encoder, f"{hparams.rewrite_module_tmp.format(layer)}.weight")
@@ -534,7 +535,7 @@ def prepare_text_encoder_edit(text_encoder, tokenizer, requests, hparams, layers
     # both run inside prepare_encoder_edit right AFTER it has launched the unedited leading layers (they need nothing but the
     # prompts), in this order
     return prepare_encoder_edit(text_encoder, tokenizer, requests, layers, hparams.rewrite_module_tmp, lam,
-                                hparams.edit_weight, targets, statistics, _shard_from_env(shard),
+                                hparams.edit_weight, targets if with_targets else None, statistics, _shard_from_env(shard),
                                 layer_module_tmp=getattr(hparams, "layer_module_tmp", None),
                                 num_edit_tokens=int(getattr(hparams, "num_edit_tokens", 1)))
 
@@ -660,7 +661,10 @@ class EditSession:
 
         sess = EditSession(pipe, hparams, device, stats_dir=..., capacity=None)
         sess.apply(requests, cache_name=...)      # same mutations / return as apply_emcid_to_text_encoder
+        sess.retain(requests, weight=1.0)         # "leave these where they are": their keys join the preserved set, no weight moves
         sess.preserved                            # M: preserved concept rows (requests x num_edit_tokens so far)
+        sess.retained                             # rows added by retain() (folded ones included)
+        sess.report()                             # report=True: what the last step did to the preserved keys and left of its residuals
         sess.fold()                               # take the M preserved rows into the session's own base factor: M -> 0
         sess.folded                               # rows folded so far (still preserved, exactly)
         sess.reset()                              # forget the preserved keys (the weights stay as they are)
@@ -686,6 +690,22 @@ class EditSession:
     keeps a copy of both for the time of the fold, so that a refused one leaves them as they were.  ``reset()`` and
     ``restore()`` drop the private factors and ``base`` and zero ``folded``.
 
+    A RETAIN list (``retain``) names concepts no step may move: a retained key is a preserved row with a zero residual, so it takes
+    the key half of a step (``hip.session_retain``: Yk, B, Lkp, T, its Cholesky, the append) and nothing else — no v* file, no
+    Stage 1, no weight read by the solver or written; every parameter is bit-identical afterwards.  The keys are the mean fc2
+    inputs at the requests' lookup rows under the weights AS THEY ARE NOW (the forward, lookups and num_edit_tokens rule of an edit
+    step), scaled by sqrt(weight edit_weight / 0.5): weight 1 counts a retained key like an edited one.  A request needs
+    ``prompts`` (or ``source_prompts``) and ``source`` only.  Capacity, ``fold()`` and ``on_full`` treat retained rows like any
+    other; with ``on_full="fold"`` a list longer than ``capacity`` is taken in chunks of at most ``capacity`` rows with a fold
+    between chunks (the weights do not change, so every chunk sees the same keys).
+
+    ``report=True`` adds one launch per edited layer to a step (``hip.session_step_norms``, from what the step left in its
+    workspace: with Z = (I + Y Y^T)^-1 [0; Rt] the step moves preserved key i by dW p_i = -Zp_i and leaves Zk_j of residual j);
+    ``report()`` reads the session's buffer (one synchronisation) and returns {weight name: {"drift": (rows preserved before the
+    step,) ||dW k_i|| in raw-key units, in the order the rows were added since the last fold — folded rows stay preserved but
+    are no longer listed —, "left": (N,) ||Zk_j|| / ||Rt_j||}}, ``None`` before any step.  ``report=False``: a step issues exactly
+    the launches it issued before.
+
     ``device``: as in apply_emcid_to_text_encoder; the state lives on the encoder's own device, ``device`` is only checked against it.
     ``capacity``: the largest M + N (default floor(0.6 d), the engine's dual / direct threshold); a step past it raises
     ``PreservedSetFull`` before anything is launched (with ``on_full="fold"``: only a step that exceeds it by itself).
@@ -695,7 +715,7 @@ class EditSession:
     non-positive pivot restores the weights and raises ``torch.linalg.LinAlgError``."""
 
     def __init__(self, pipe, hparams: EMCIDHyperParams, device: Optional[str] = None, stats_dir=STATS_DIR,
-                 capacity: Optional[int] = None, verbose: bool = False, on_full: str = "raise"):
+                 capacity: Optional[int] = None, verbose: bool = False, on_full: str = "raise", report: bool = False):
         if on_full not in ("raise", "fold"):
             raise ValueError(f"on_full must be 'raise' or 'fold' (got {on_full!r})")
         if isinstance(hparams, EMCIDXLHyperParams) or getattr(pipe, "text_encoder_2", None) is not None:
@@ -737,6 +757,9 @@ class EditSession:
         self.private_factors: Optional[hip.CovFactors] = None    # the factors of lam C' + (folded P)^T P: this session's steps only
         self._base: Optional[torch.Tensor] = None            # (n_layers, dp, dp) f64: the folded systems themselves
         self._shared = None     # (factors, covs) of the last sound step: what the preserved rows' coordinates refer to
+        self.retained = 0                                    # rows added by retain(), folded ones included
+        self.report_on = bool(report)
+        self._report = self._report_pending = None           # (buffer (n_layers, M + 2 N) f64 in HBM, M, N, row scales) of the last sound step
 
     @property
     def preserved(self) -> int:
@@ -788,18 +811,41 @@ class EditSession:
         if self.verbose:
             print(f"Session fold {self.folds}: {M} preserved rows folded into the base factor, {self.folded} folded so far")
 
-    def workspace(self, N: int, d: int, h: int, dev) -> "hip.PreserveWorkspace":
-        """(engine side) the workspace of a step of N rows; the two most recent step sizes keep theirs"""
-        key = (N, d, h, str(dev))
+    def workspace(self, N: int, d: int, h: int, dev, retain: bool = False):
+        """(engine side) the workspace of a step (``retain``: of a retain call) of N rows; the two most recent sizes keep theirs"""
+        key = (N, d, h, str(dev), bool(retain))
         ws = self._ws.pop(key, None)
         if ws is None:
-            ws = hip.PreserveWorkspace(N, d, h, self.capacity, dev)
+            ws = hip.RetainWorkspace(N, d, self.capacity, dev) if retain else hip.PreserveWorkspace(N, d, h, self.capacity, dev)
             while len(self._ws) >= 2:
                 self._ws.pop(next(iter(self._ws)))
         self._ws[key] = ws
         return ws
 
-    def _check_step(self, requests, shard):
+    def report_row(self, i: int, N: int) -> torch.Tensor:
+        """(engine side) where edited layer ``i`` of the step in flight writes its M + 2 N norms"""
+        if self._report_pending is None:
+            M = self.preserved
+            buf = torch.empty(len(self._fixed[2]), M + 2 * N, dtype=torch.float64, device=self.keys.Yp[0].device)
+            self._report_pending = (buf, M, N, self.keys.row_scale[:M].clone())
+        return self._report_pending[0][i]
+
+    def report(self):
+        """The readout of the last sound step of a ``report=True`` session (class docstring), ``None`` before any."""
+        if self._report is None:
+            return None
+        buf, M, N, scale = self._report
+        host = buf.cpu()                            # the one synchronising read
+        out = {}
+        for i, l in enumerate(self._fixed[2]):
+            row = host[i]
+            resid = row[M + N:M + 2 * N]
+            out[f"{self.hparams.rewrite_module_tmp.format(l)}.weight"] = {
+                "drift": row[:M] / scale,
+                "left": torch.where(resid > 0, row[M:M + N] / resid.clamp(min=torch.finfo(torch.float64).tiny), torch.zeros_like(resid))}
+        return out
+
+    def _check_call(self, requests, shard, what="a session step"):
         hp = self.hparams
         now = (float(hp.mom2_update_weight), float(hp.edit_weight), tuple(hp.layers), int(getattr(hp, "num_edit_tokens", 1)))
         if now != self._fixed:
@@ -811,7 +857,10 @@ class EditSession:
         if forced in ("direct", "lu"):
             raise ValueError(f"EMCID_SOLVER={forced} inside a session: the preserved keys live in the dual solver's coordinates")
         if len(requests) == 0:
-            raise ValueError("a session step needs at least one request")
+            raise ValueError(f"{what} needs at least one request")
+
+    def _check_step(self, requests, shard):
+        self._check_call(requests, shard)
         n = len(requests) * self._fixed[3]
         if self.preserved + n > self.capacity and self.on_full == "fold" and n <= self.capacity:
             return n                                # apply() folds first
@@ -848,6 +897,7 @@ class EditSession:
                                              cache_name, "", self.verbose, shard, _default_stage1(self.pipe, hp, stage1))
             plan.session = self
             stats_flag = None
+            self._report_pending = None
             try:
                 try:
                     with phase("run + final sync"):
@@ -874,8 +924,11 @@ class EditSession:
                     f"session step {self.steps}: {what} ({e}); the edited weights have been restored and nothing was added to "
                     f"the {self.preserved} preserved rows") from e
             break
-        self.keys.commit(n)                         # all edited layers together: their rows are already behind row M
+        # all edited layers together: their rows are already behind row M
+        self.keys.commit(n, hip.row_scale_of(self._fixed[1], plan.cov_factors, self._fixed[0]))
         self.steps += 1
+        if self._report_pending is not None:
+            self._report, self._report_pending = self._report_pending, None
         if self.private_factors is None:            # the workspace this step's rows are coordinates of, and its statistics
             self._shared = (plan.cov_factors, [plan.covs[l] for l in plan.layers])
         LP["session_steps"], LP["session_preserved_rows"] = self.steps, self.keys.M
@@ -884,15 +937,92 @@ class EditSession:
             print(f"Session step {self.steps}: {n} concept rows inserted, {self.keys.M} preserved")
         return self.pipe, origin_text_encoder
 
+    def retain(self, requests: List[Dict], weight: float = 1.0, shard=None) -> int:
+        """Enter the keys of ``requests`` into the preserved set with a zero residual: later steps leave these concepts where they
+        are (class docstring).  ``weight``: how much a retained key counts against an edited one (finite, > 0).  No parameter of the
+        encoder changes.  Returns the rows added (len(requests) x num_edit_tokens).  Refuses what ``apply`` refuses; with
+        ``on_full="raise"`` a list that does not fit raises ``PreservedSetFull`` before anything is launched, with ``"fold"`` the set
+        is folded first, and a list longer than ``capacity`` goes in chunks with a fold between them.  A non-positive pivot raises
+        ``torch.linalg.LinAlgError`` with nothing committed (of the chunk in flight)."""
+        try:
+            w = float(weight)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"weight must be a positive finite number (got {weight!r})") from e
+        if not (np.isfinite(w) and w > 0.0):
+            raise ValueError(f"weight must be a positive finite number (got {weight!r})")
+        self._check_call(requests, shard, "a retain list")
+        k = self._fixed[3]
+        n, per = len(requests) * k, self.capacity // k
+        if self.preserved + n <= self.capacity:
+            chunks = [list(requests)]
+        elif self.on_full == "fold" and per >= 1:
+            chunks = [list(requests[a:a + per]) for a in range(0, len(requests), per)]
+        else:
+            raise PreservedSetFull(f"{self.preserved} preserved + {n} retained concept rows exceed the session's capacity "
+                                   f"{self.capacity}; open a session with a larger capacity, or with on_full='fold' (the list is "
+                                   f"then taken in chunks, the set folded into the session's base factor between them)")
+        for chunk in chunks:
+            self._retain_chunk(chunk, w, shard)
+        return n
+
+    def _retain_chunk(self, requests, w, shard):
+        n = len(requests) * self._fixed[3]
+        if self.preserved + n > self.capacity:
+            self.fold()
+        hp, te = self.hparams, self.pipe.text_encoder
+        if self.keys is None:
+            wt = next(iter(self._weights().values()))
+            if not wt.is_cuda:
+                raise hip.EmcidHipError(f"the text encoder must live in HBM (got {wt.device}); there is no CPU path")
+            self.keys = hip.PreservedKeys(len(self._fixed[2]), self.d, self.capacity, wt.device)
+        LP = clip_forward.LAST_PATHS
+        for attempt in (0, 1):
+            plan = prepare_text_encoder_edit(te, self.pipe.tokenizer, requests, hp, hp.layers, hp.mom2_update_weight, self.stats_dir,
+                                             None, "", self.verbose, shard, None, with_targets=False)
+            plan.session, plan.retain_weight = self, w
+            stats_flag = None
+            try:
+                try:
+                    with phase("run + final sync"):
+                        run_encoder_edit(plan, keep_factors=False, restore=False)       # (writes no weight)
+                except BaseException:
+                    edit_engine._release_workspaces(plan)
+                    raise
+                stats_flag = plan.cov_factors.info if plan.cov_factors is not None else None
+                check_info(plan)
+            except clip_forward.StaleWeightCacheError as e:
+                if attempt == 1:
+                    raise
+                logging.getLogger("emcid_amd").warning("EditSession.retain: %s; redoing the call from the live weights", e)
+                clip_forward.invalidate_weight_caches(None)
+                LP["stale_cache_retries"] = LP.get("stale_cache_retries", 0) + 1
+                continue
+            except FloatingPointError as e:
+                what = "the statistics lam C' themselves are not positive definite" if stats_flag is not None and int(stats_flag.item()) \
+                    else f"the system of the retained keys given the {self.preserved} preserved ones is not positive definite"
+                raise torch.linalg.LinAlgError(
+                    f"retain after step {self.steps}: {what} ({e}); nothing was added to the {self.preserved} preserved rows") from e
+            break
+        self.keys.commit(n, hip.row_scale_of(self._fixed[1], plan.cov_factors, self._fixed[0], w))
+        self.retained += n
+        if self.private_factors is None:
+            self._shared = (plan.cov_factors, [plan.covs[l] for l in plan.layers])
+        LP["session_preserved_rows"], LP["session_retained_rows"] = self.keys.M, self.retained
+        LP["session_folds"], LP["session_folded_rows"] = self.folds, self.folded
+        if self.verbose:
+            print(f"Session retain: {n} concept rows retained at weight {w:g}, {self.keys.M} preserved")
+
     def reset(self):
         """Forget the preserved keys; the weights stay as they are, the next step starts a fresh set (M = 0)."""
         if self.keys is not None:
             self.keys.reset()
         self.steps = 0
         self.private_factors = self._base = self._shared = None
-        self.folded = self.folds = 0
+        self.folded = self.folds = self.retained = 0
+        self._report = self._report_pending = None
         LP = clip_forward.LAST_PATHS
         LP["session_steps"] = LP["session_preserved_rows"] = LP["session_folds"] = LP["session_folded_rows"] = 0
+        LP["session_retained_rows"] = 0
 
     def restore(self):
         """The edited weights back at their values of before the session's first step (bit-identical), and the keys forgotten."""

@@ -6,6 +6,7 @@ torch is used here only to hand over device pointers and the current HIP stream.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import threading
 from pathlib import Path
@@ -28,6 +29,7 @@ EXPORTS = [
     "emcid_edit_dual_apply_stage1_f64", "emcid_edit_dual_yt", "emcid_edit_dual_apply_stage2_f64",
     "emcid_edit_dual_apply_assemble_f64",
     "emcid_edit_dual_preserve_workspace_bytes", "emcid_edit_layer_dual_preserve_f64",
+    "emcid_session_retain_workspace_bytes", "emcid_session_retain_f64", "emcid_session_step_norms_f64",
     "emcid_cov_factor_fold_workspace_bytes", "emcid_cov_factor_fold_f64",
     "emcid_edit_lu_workspace_bytes", "emcid_edit_layer_lu_f64", "emcid_lu_solve_f64",
     "emcid_edit_dual_cols_stage1_f64", "emcid_edit_dual_s", "emcid_edit_dual_u", "emcid_edit_dual_cols_stage2_f64",
@@ -92,6 +94,9 @@ def load():
         "emcid_edit_dual_preserve_workspace_bytes": (i64, [i64, i64, i64, i64]),
         "emcid_edit_layer_dual_preserve_f64": (i32, [p, p, p, i64, i64, i64, f64, i32, f64, p, i64, i64, p, i64, p, i64, p, i64, i64,
                                                      p, p, p, p, p, i64, p, p]),
+        "emcid_session_retain_workspace_bytes": (i64, [i64, i64, i64]),
+        "emcid_session_retain_f64": (i32, [p, i64, i64, f64, f64, p, i64, i64, p, i64, p, i64, p, i64, i64, p, i64, p, p]),
+        "emcid_session_step_norms_f64": (i32, [p, i64, i64, i64, i64, i64, i64, p, p, p, p]),
         "emcid_cov_factor_fold_workspace_bytes": (i64, [i64, i64]),
         "emcid_cov_factor_fold_f64": (i32, [p, f64, p, i64, i64, i64, p, f64, f64, i32, p, i64, i64, i64, p, p, i64, p, p]),
         "emcid_cholesky_solve_f64": (i32, [p, i64, i64, p, p, p, i64, i64, p]),
@@ -1238,7 +1243,10 @@ class PreservedKeys:
     """The session state of the dual solver for ``n_layers`` edited layers (include/emcid_hip.h, "PRESERVED key set"): per layer
     Yp (capacity, dp), Lp (capacity, capacity) and the inverses of Lp's diagonal 128-tiles, f64 in HBM, allocated once —
     capacity * dp + capacity^2 doubles per layer plus the tiles.  ``M`` rows of every layer are committed; ``edit_layer_dual_preserve``
-    writes a step's rows behind them and ``commit(N)`` makes them count."""
+    (an edit's rows) and ``session_retain`` (a retain list's) write rows behind them and ``commit(N, scale)`` makes them count.
+    ``row_scale`` (capacity,) f64 on the host: the factor each committed row's raw key was multiplied by on its way in
+    (sqrt(edit_weight / 0.5) / sqrt(lam_ratio) for an edited key, with the retain weight under the first root for a retained one) —
+    what takes a norm in the solve's units back to raw-key units (``session_step_norms``); the same for every layer."""
 
     def __init__(self, n_layers: int, d: int, capacity: int, device):
         if capacity < 1:
@@ -1250,9 +1258,11 @@ class PreservedKeys:
         self.Yp = [torch.zeros(self.capacity, self.dp, dtype=torch.float64, device=device) for _ in range(n_layers)]
         self.Lp = [torch.zeros(self.capacity, self.ldl, dtype=torch.float64, device=device) for _ in range(n_layers)]
         self.tile_inv = [torch.zeros(tiles, NB, NB, dtype=torch.float64, device=device) for _ in range(n_layers)]
+        self.row_scale = torch.ones(self.capacity, dtype=torch.float64)
 
-    def commit(self, N: int):
+    def commit(self, N: int, scale: float = 1.0):
         assert self.M + N <= self.capacity
+        self.row_scale[self.M:self.M + int(N)] = float(scale)
         self.M += int(N)
 
     def reset(self):
@@ -1305,6 +1315,78 @@ def edit_layer_dual_preserve(K, Zc, zs_t, factors: CovFactors, layer_index: int,
         state.capacity, state.M, _ptr(W0, torch.float32, "W0"), _ptr(W, torch.float32, "W"), _ptr(dW), _ptr(U),
         _ptr(ws.buf), ws.nbytes, _ptr(ws.info, torch.int32), _stream(K)), "emcid_edit_layer_dual_preserve_f64")
     return {"dW": dW, "U": U, "ws": ws}
+
+
+class RetainWorkspace:
+    """HBM workspace (+ the device `info` word) of emcid_session_retain_f64 for retain calls of N rows at a given capacity."""
+
+    def __init__(self, N: int, d: int, capacity: int, device):
+        self.key = (N, d, capacity)
+        self.nbytes = int(load().emcid_session_retain_workspace_bytes(N, d, capacity))
+        if self.nbytes <= 0:
+            raise EmcidHipError(f"no retain workspace for N={N}, d={d}, capacity={capacity}")
+        self.buf = torch.zeros(self.nbytes // 8, dtype=torch.float64, device=device)     # zero: the stream-K ticket counters
+        self.info = torch.zeros(1, dtype=torch.int32, device=device)
+
+
+def row_scale_of(edit_weight: float, factors: CovFactors, lam: Optional[float] = None, weight: float = 1.0) -> float:
+    """The factor a raw key is multiplied by on its way into a preserved key set (``PreservedKeys.row_scale``): sqrt(weight
+    edit_weight / 0.5), the ``row_scale`` of ``session_retain`` (weight 1: an edited key's), over sqrt(lam_ratio)."""
+    return math.sqrt(float(weight) * float(edit_weight) / 0.5) / math.sqrt(factors.lam_ratio(lam))
+
+
+def session_retain(K, factors: CovFactors, layer_index: int, row_scale: float, state: PreservedKeys,
+                   ws: Optional[RetainWorkspace] = None, lam: Optional[float] = None):
+    """A retain list for layer ``layer_index`` of ``state``: the rows of K (N, d) fp32, scaled by ``row_scale``, enter the
+    preserved key set with a zero residual — Yk, [Lkp Lkk] and the touched tile inverses land behind ``state.M``; no weight is
+    read or written (include/emcid_hip.h, emcid_session_retain_f64).  Nothing is committed here (``state.commit(N, scale)`` after the
+    flag word ``ws.info`` read zero, for all layers together).  Needs the layer's explicit inverse factor.  Returns dict(ws)."""
+    N, d = K.shape
+    assert K.is_contiguous(), "K"
+    assert factors.d == d == state.d
+    if not 0 <= layer_index < state.n_layers:
+        raise EmcidHipError(f"layer index {layer_index} outside the session state's {state.n_layers} layers")
+    if layer_index not in factors.have_inverse:
+        raise EmcidHipError("session_retain needs the explicit inverse factor of the layer (cov_inverse)")
+    if state.M + N > state.capacity:
+        raise EmcidHipError(f"{state.M} preserved + {N} retained rows exceed the state's capacity {state.capacity}")
+    row_scale = float(row_scale)
+    if not (row_scale > 0.0 and row_scale < float("inf")):
+        raise EmcidHipError(f"row_scale must be positive and finite (got {row_scale})")
+    if ws is None or ws.key != (N, d, state.capacity):
+        ws = RetainWorkspace(N, d, state.capacity, K.device)
+    Yp, Lp, Ti = state.Yp[layer_index], state.Lp[layer_index], state.tile_inv[layer_index]
+    for t, nm in ((Yp, "Yp"), (Lp, "Lp"), (Ti, "tile_inv")):
+        assert t.stride(-1) == 1 and (t.dim() < 3 or t.is_contiguous()), nm
+    _check(load().emcid_session_retain_f64(
+        _ptr(K, torch.float32, "K"), N, d, row_scale, factors.lam_ratio(lam), _ptr(factors.buf), factors.n_layers, int(layer_index),
+        _ptr(Yp, torch.float64, "Yp"), Yp.stride(0), _ptr(Lp, torch.float64, "Lp"), Lp.stride(0), _ptr(Ti, torch.float64, "tile_inv"),
+        state.capacity, state.M, _ptr(ws.buf), ws.nbytes, _ptr(ws.info, torch.int32), _stream(K)), "emcid_session_retain_f64")
+    return {"ws": ws}
+
+
+def session_step_norms(ws: PreserveWorkspace, N: int, d: int, h: int, state: PreservedKeys, out: Optional[torch.Tensor] = None):
+    """The readout of the ``edit_layer_dual_preserve`` call that has just run on ``ws`` (same N, d, h, ``state.M`` not yet
+    committed, the same stream): one launch, no synchronisation.  Returns dict(drift (M,), left (N,), resid (N,)) f64 in HBM:
+    ||Zp_i||, ||Zk_j||, ||Rt_j|| in the solve's scaled units — the step moved preserved key i by ||dW k_i|| = drift[i] /
+    state.row_scale[i] and left the fraction left[j] / resid[j] of new residual j.  ``out``: a contiguous f64 tensor of at least
+    M + 2 N elements on the device to write into (the three results are views of it)."""
+    N, M = int(N), int(state.M)
+    if not isinstance(ws, PreserveWorkspace) or ws.key != (N, int(d), int(h), state.capacity):
+        raise EmcidHipError(f"session_step_norms reads the workspace of the preserve step of N={N}, d={d}, h={h} at capacity "
+                            f"{state.capacity} (got {getattr(ws, 'key', None)})")
+    if M + N > state.capacity:
+        raise EmcidHipError(f"{M} preserved + {N} new rows exceed the state's capacity {state.capacity}")
+    if out is None:
+        out = torch.empty(M + 2 * N, dtype=torch.float64, device=ws.buf.device)
+    if out.dtype != torch.float64 or not out.is_contiguous() or out.numel() < M + 2 * N or out.device != ws.buf.device:
+        raise EmcidHipError(f"session_step_norms: out must be a contiguous f64 tensor of >= {M + 2 * N} elements on {ws.buf.device}")
+    flat = out.view(-1)
+    drift, left, resid = flat[:M], flat[M:M + N], flat[M + N:M + 2 * N]
+    _check(load().emcid_session_step_norms_f64(
+        _ptr(ws.buf), ws.nbytes, N, int(d), int(h), state.capacity, M, _ptr(drift, torch.float64, "drift") if M > 0 else None,
+        _ptr(left, torch.float64, "left"), _ptr(resid, torch.float64, "resid"), _stream(ws.buf)), "emcid_session_step_norms_f64")
+    return {"drift": drift, "left": left, "resid": resid}
 
 
 def cov_factor_fold(src: CovFactors, state: PreservedKeys, layer_index: int, cov: Optional[torch.Tensor], lam: float,

@@ -396,6 +396,32 @@ int emcid_edit_layer_dual_preserve_f64(const float* K, const float* Zc, const fl
                                        double* tile_inv, int64_t capacity, int64_t M, const float* W0, float* W, float* dW_out,
                                        double* U_out, void* workspace, int64_t workspace_bytes, int* info_dev, void* stream);
 
+/* A RETAIN list for a preserved key set (edit sessions: "leave these concepts where they are"; entry points added under ABI 16).
+ * A retained key is a preserved row with a zero residual, so it takes the first half of the step above and nothing else:
+ *     Kt64 = row_scale K   (converted as stage 1 converts an edit's keys, lam_ratio applied the same way),   Yk = Kt64 X^T,
+ *     B = Yk Yp^T,  Lkp = B Lp^-T,  T = I + Yk Yk^T - Lkp Lkp^T = Lkk Lkk^T
+ * and Yk, [Lkp Lkk] and the touched tile inverses are written behind row M.  With Rt = 0 the step's Zk, Zp and U are zero: that
+ * half is not run, and no Zc, targets or weights are arguments.  ONE layer per call.  row_scale: sqrt(weight * edit_weight / 0.5)
+ * makes a retained key count `weight` times an edited one.  The contract is that of emcid_edit_layer_dual_preserve_f64: rows
+ * < M are never written, the caller commits by passing M + N next time and must not when info_dev reports a non-positive pivot
+ * of T, no host synchronisation, M + N <= capacity, X = inv(L) of the layer is needed.  Yp / Lp / tile_inv: layout, type and
+ * meaning as above.  workspace: emcid_session_retain_workspace_bytes(N, d, capacity) (0: no such workspace). */
+int64_t emcid_session_retain_workspace_bytes(int64_t N, int64_t d, int64_t capacity);
+int emcid_session_retain_f64(const float* K, int64_t N, int64_t d, double row_scale, double lam_ratio, const void* cov_factor_ws,
+                             int64_t n_layers, int64_t layer_index, double* Yp, int64_t ldy, double* Lp, int64_t ldl,
+                             double* tile_inv, int64_t capacity, int64_t M, void* workspace, int64_t workspace_bytes, int* info_dev,
+                             void* stream);
+
+/* The readout of a preserve step, from what it left in its workspace.  With Z = (I + Y Y^T)^-1 [0; Rt] (Y = [Yp; Yk]) the step
+ * moves every preserved key by dW p_i = -Zp_i and leaves Zk_j of each new residual; ZT = [Zp^T | Zk^T] and Rt are still in the
+ * workspace when the step returns.  Called stream-ordered right after emcid_edit_layer_dual_preserve_f64 on the SAME workspace
+ * with the same N, d, h, capacity and M; one launch:
+ *     drift_out [M] = ||Zp_i||_2     left_out [N] = ||Zk_j||_2     resid_out [N] = ||Rt_j||_2
+ * in the scaled units of the solve (a preserved row entered as Kt64 = scale K / sqrt(lam_ratio); Rt carries the same factors).
+ * drift_out may be null when M == 0.  f64 in HBM; the workspace is only read. */
+int emcid_session_step_norms_f64(const void* workspace, int64_t workspace_bytes, int64_t N, int64_t d, int64_t h, int64_t capacity,
+                                 int64_t M, double* drift_out, double* left_out, double* resid_out, void* stream);
+
 /* Fold a preserved key set into a base factor the caller owns (ABI 16; edit sessions whose set is full).  For ONE layer:
  *     Q = Yp L_s^T,  L_s = sqrt(lam_ratio) L_src    the M preserved (scaled) keys back from factor coordinates; lam_ratio = the
  *                                                    caller's lam / the lam src_ws was factored with, exact for any ratio
