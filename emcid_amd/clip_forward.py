@@ -47,7 +47,7 @@ SPLIT_GEMM = os.environ.get("EMCID_SPLIT_GEMM", "1") != "0"
 LAST_PATHS = {"linear_sp16": 0, "linear_f32": 0, "linear_torch": 0, "native_layers": 0, "fused_edit_layers": 0, "forward_trie": 0,
               "forward_hf": 0, "forward_hf_fallback": 0, "sweep_points": 0, "sweep_cov_factorizations": 0, "sweep_prefix_runs": 0,
               "session_steps": 0, "session_preserved_rows": 0, "session_folds": 0, "session_folded_rows": 0,
-              "session_retained_rows": 0}
+              "session_retained_rows": 0, "session_released_rows": 0}
 _FALLBACK_SEEN = set()
 
 

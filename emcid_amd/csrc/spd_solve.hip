@@ -104,6 +104,18 @@ __global__ __launch_bounds__(256) void step_norms_kernel(const double* __restric
     }
 }
 
+// dst[j][0:dp] = src[idx[j]][0:dp] for j < n, zero for the padding rows n <= j < gridDim.x (emcid_session_release_f64: the kept rows
+// of Yp, gathered through the workspace because they overlap their destination).  One workgroup per row, double2; src, dst 16-byte
+// aligned, lds_ and dp even.  An index outside [0, rows) reads nothing: the row is zeroed.
+__global__ __launch_bounds__(256) void gather_rows_f64_kernel(const double* __restrict__ src, int64_t lds_, const int32_t* __restrict__ idx,
+                                                               int n, int rows, double* __restrict__ dst, int dp) {
+    const int j = blockIdx.x;
+    const int r = j < n ? idx[j] : -1;
+    const double2* s = r >= 0 && r < rows ? reinterpret_cast<const double2*>(src + (int64_t)r * lds_) : nullptr;
+    double2* o = reinterpret_cast<double2*>(dst + (int64_t)j * dp);
+    for (int c = threadIdx.x; c < dp / 2; c += 256) o[c] = s ? s[c] : make_double2(0.0, 0.0);
+}
+
 __global__ __launch_bounds__(256) void copy2d_f64_kernel(const double* __restrict__ src, int64_t lds_, double* __restrict__ dst,
                                                           int64_t ldd, int rows, int cols, double scale = 1.0) {
     const int r = blockIdx.x;
@@ -2664,38 +2676,14 @@ int emcid_edit_layer_dual_preserve_f64(const float* K, const float* Zc, const fl
     return EMCID_OK;
 }
 
-/* ---- edit sessions: a RETAIN list — preserved rows with a zero residual -------------------------------------------------------
- * The first half of emcid_edit_layer_dual_preserve_f64 for keys that are to stay where they are: Yk, B, Lkp, T, its Cholesky and
- * the append behind row M.  With Rt = 0 the step's Zk, Zp and U vanish identically, so that half is not run at all: no Zc, no
- * targets, no weights. */
-int64_t emcid_session_retain_workspace_bytes(int64_t N, int64_t d, int64_t capacity) {
-    if (N <= 0 || d <= 0 || capacity < N) return 0;
-    return RetainWorkspace(N, d, capacity).total * (int64_t)sizeof(double);
-}
-
-int emcid_session_retain_f64(const float* K, int64_t N, int64_t d, double row_scale, double lam_ratio, const void* cov_factor_ws,
-                             int64_t n_layers, int64_t layer_index, double* Yp, int64_t ldy, double* Lp, int64_t ldl,
-                             double* tile_inv, int64_t capacity, int64_t M, void* workspace, int64_t workspace_bytes, int* info_dev,
-                             void* stream) {
-    EMCID_CHECK_ARG(K && N > 0 && d > 0 && Yp && Lp && tile_inv && workspace && info_dev && cov_factor_ws);
-    EMCID_CHECK_ARG(0 <= layer_index && layer_index < n_layers && row_scale > 0.0 && row_scale < 1e150);
-    EMCID_CHECK_ARG(lam_ratio > 0.0 && lam_ratio < 1e300);
-    EMCID_CHECK_ARG(M >= 0 && M + N <= capacity && capacity < (int64_t)1 << 30);
-    RetainWorkspace ws(N, d, capacity);
-    EMCID_CHECK_ARG(ldy >= ws.dp && ldy % 2 == 0 && ldl >= capacity && ldl % 2 == 0 && aligned16(Yp) && aligned16(Lp) && aligned16(tile_inv));
-    if (workspace_bytes < ws.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    double* base = (double*)workspace;
-    double *Kt = base + ws.off_K, *Yt = base + ws.off_Y, *S = base + ws.off_S, *LS = base + ws.off_LS, *invS = base + ws.off_invS;
+// The key half of a step behind row M, from N rows that already are in factor coordinates (Yt [Np][dp] in the workspace): the
+// copy into Yp, B, Lkp, T, its Cholesky (the explicit inverse riding in it as in a preserve step), the append and the tile
+// inverses.  emcid_session_retain_f64 and emcid_session_release_f64 both end in it.
+static int session_append_rows(const RetainWorkspace& ws, double* base, int64_t N, double* Yp, int64_t ldy, double* Lp, int64_t ldl,
+                               double* tile_inv, int64_t M, int* info_dev, hipStream_t st, const char* who) {
+    double *Yt = base + ws.off_Y, *S = base + ws.off_S, *LS = base + ws.off_LS, *invS = base + ws.off_invS;
     double *XT = base + ws.off_XT, *TT = base + ws.off_TT, *Bw = base + ws.off_B;
     const int64_t dp = ws.dp, Np = ws.Np, cp = ws.cp;
-    {
-        ScopedProf sp(KC_PREP, st);
-        hipLaunchKernelGGL(prep_k_kernel, dim3((unsigned)Np), dim3(256), 0, st, K, (int)N, (int)d, row_scale, Kt, (int)dp,
-                           1.0 / sqrt(lam_ratio));
-    }
-    // Yt = Kt64 X^T over the Np padded rows, as stage 1 of the apply-only form runs the whole concept range
-    apply_inverse_forward(cov_inverse(cov_factor_ws, n_layers, dp, layer_index), dp, Kt, Yt, (int)Np, st, base + ws.off_SK);
     double* Yk = Yp + M * ldy;
     double* Lkp = Lp + M * ldl;
     hipLaunchKernelGGL(copy2d_f64_kernel, dim3((unsigned)N), dim3(256), 0, st, Yt, dp, Yk, ldy, (int)N, (int)dp, 1.0);
@@ -2719,8 +2707,66 @@ int emcid_session_retain_f64(const float* K, int64_t N, int64_t d, double row_sc
         const unsigned tiles = (unsigned)((M + N - 1) / NB - M / NB + 1);
         hipLaunchKernelGGL(tile_inverse_extend_kernel, dim3(tiles, NB / 16), dim3(64), 0, st, Lp, ldl, tile_inv, (int)M, (int)(M + N));
     }
-    EMCID_CHECK_LAUNCH();
-    return EMCID_OK;
+    return check_launch(who);
+}
+
+/* ---- edit sessions: a RETAIN list — preserved rows with a zero residual -------------------------------------------------------
+ * The first half of emcid_edit_layer_dual_preserve_f64 for keys that are to stay where they are: Yk, B, Lkp, T, its Cholesky and
+ * the append behind row M.  With Rt = 0 the step's Zk, Zp and U vanish identically, so that half is not run at all: no Zc, no
+ * targets, no weights. */
+int64_t emcid_session_retain_workspace_bytes(int64_t N, int64_t d, int64_t capacity) {
+    if (N <= 0 || d <= 0 || capacity < N) return 0;
+    return RetainWorkspace(N, d, capacity).total * (int64_t)sizeof(double);
+}
+
+int emcid_session_retain_f64(const float* K, int64_t N, int64_t d, double row_scale, double lam_ratio, const void* cov_factor_ws,
+                             int64_t n_layers, int64_t layer_index, double* Yp, int64_t ldy, double* Lp, int64_t ldl,
+                             double* tile_inv, int64_t capacity, int64_t M, void* workspace, int64_t workspace_bytes, int* info_dev,
+                             void* stream) {
+    EMCID_CHECK_ARG(K && N > 0 && d > 0 && Yp && Lp && tile_inv && workspace && info_dev && cov_factor_ws);
+    EMCID_CHECK_ARG(0 <= layer_index && layer_index < n_layers && row_scale > 0.0 && row_scale < 1e150);
+    EMCID_CHECK_ARG(lam_ratio > 0.0 && lam_ratio < 1e300);
+    EMCID_CHECK_ARG(M >= 0 && M + N <= capacity && capacity < (int64_t)1 << 30);
+    RetainWorkspace ws(N, d, capacity);
+    EMCID_CHECK_ARG(ldy >= ws.dp && ldy % 2 == 0 && ldl >= capacity && ldl % 2 == 0 && aligned16(Yp) && aligned16(Lp) && aligned16(tile_inv));
+    if (workspace_bytes < ws.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    double* base = (double*)workspace;
+    double *Kt = base + ws.off_K, *Yt = base + ws.off_Y;
+    const int64_t dp = ws.dp, Np = ws.Np;
+    {
+        ScopedProf sp(KC_PREP, st);
+        hipLaunchKernelGGL(prep_k_kernel, dim3((unsigned)Np), dim3(256), 0, st, K, (int)N, (int)d, row_scale, Kt, (int)dp,
+                           1.0 / sqrt(lam_ratio));
+    }
+    // Yt = Kt64 X^T over the Np padded rows, as stage 1 of the apply-only form runs the whole concept range
+    apply_inverse_forward(cov_inverse(cov_factor_ws, n_layers, dp, layer_index), dp, Kt, Yt, (int)Np, st, base + ws.off_SK);
+    return session_append_rows(ws, base, N, Yp, ldy, Lp, ldl, tile_inv, M, info_dev, st, __func__);
+}
+
+/* ---- edit sessions: RELEASE rows of the preserved set ----------------------------------------------------------------------------
+ * keep[0 .. n_keep) are the rows that stay, ascending, keep[j] == j below `first` (the smallest released index).  Rows < first of
+ * Yp, Lp and the tile inverses already are the state of the reduced set (the leading rows of a Cholesky factor do not depend on
+ * later ones).  The kept rows behind `first` are gathered into the workspace's Yt block — source and destination rows overlap in
+ * Yp — and re-enter as the key half of a step with M = first, N = n_keep - first: no forward, no X, no statistics, no weights. */
+int64_t emcid_session_release_workspace_bytes(int64_t n_rebuilt, int64_t d, int64_t capacity) {
+    return emcid_session_retain_workspace_bytes(n_rebuilt, d, capacity);
+}
+
+int emcid_session_release_f64(const int32_t* keep_dev, int64_t n_keep, int64_t first, int64_t d, double* Yp, int64_t ldy, double* Lp,
+                              int64_t ldl, double* tile_inv, int64_t capacity, int64_t M, void* workspace, int64_t workspace_bytes,
+                              int* info_dev, void* stream) {
+    EMCID_CHECK_ARG(keep_dev && d > 0 && Yp && Lp && tile_inv && workspace && aligned16(workspace) && info_dev);
+    EMCID_CHECK_ARG(first >= 0 && first < n_keep && n_keep < M && M <= capacity && capacity < (int64_t)1 << 30);
+    const int64_t N = n_keep - first;
+    RetainWorkspace ws(N, d, capacity);
+    EMCID_CHECK_ARG(ldy >= ws.dp && ldy % 2 == 0 && ldl >= capacity && ldl % 2 == 0 && aligned16(Yp) && aligned16(Lp) && aligned16(tile_inv));
+    if (workspace_bytes < ws.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    double* base = (double*)workspace;
+    hipLaunchKernelGGL(gather_rows_f64_kernel, dim3((unsigned)ws.Np), dim3(256), 0, st, Yp, ldy, keep_dev + first, (int)N, (int)M,
+                       base + ws.off_Y, (int)ws.dp);
+    return session_append_rows(ws, base, N, Yp, ldy, Lp, ldl, tile_inv, first, info_dev, st, __func__);
 }
 
 /* The readout of the preserve step that has just run on `workspace` (same N, d, h, capacity, M, same stream): the step left

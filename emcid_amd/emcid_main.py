@@ -654,6 +654,31 @@ class PreservedSetFull(RuntimeError):
     """A step of an ``EditSession`` would take the preserved key set past the session's capacity; nothing was launched."""
 
 
+def release_plan(ledger, folded_sources, sources):
+    """The host half of ``EditSession.release``, pure: ``ledger`` is the session's row ledger (one ``(source, kind, ordinal, token
+    index)`` tuple per live row, in row order), ``folded_sources`` the names whose rows a fold took, ``sources`` the names to
+    release.  Returns (keep: ascending indices of the rows that stay, first: the smallest released index, retained: how many of
+    the released rows a retain list had added).  ``ValueError`` for an empty list and for a folded source, ``KeyError`` for an
+    unknown one — folded is looked at first only for names without live rows, so a name re-entered after a fold can go."""
+    names = list(sources)
+    if not names:
+        raise ValueError("a release needs at least one source")
+    live = {row[0] for row in ledger}
+    for name in names:
+        if name in live:
+            continue
+        if name in folded_sources:
+            raise ValueError(f"source {name!r} was folded: its keys live inside the session's base factor and the session no longer "
+                             f"has their rows; releasing across a fold is not supported — restore() gives the original weights back "
+                             f"and forgets every key")
+        raise KeyError(f"source {name!r} has no preserved row in this session")
+    gone = set(names)
+    keep = [i for i, row in enumerate(ledger) if row[0] not in gone]
+    first = next((j for j, i in enumerate(keep) if i != j), len(keep))
+    retained = sum(1 for row in ledger if row[0] in gone and row[1] == "retain")
+    return keep, first, retained
+
+
 class EditSession:
     """A sequence of ``apply_emcid_to_text_encoder`` calls on ONE text encoder in which every later edit keeps the keys of the
     earlier ones: step t solves against lam C' + P^T P + Kt^T Kt, P the stacked (scaled) keys of steps < t, where two plain calls
@@ -665,6 +690,8 @@ class EditSession:
         sess.preserved                            # M: preserved concept rows (requests x num_edit_tokens so far)
         sess.retained                             # rows added by retain() (folded ones included)
         sess.report()                             # report=True: what the last step did to the preserved keys and left of its residuals
+        sess.release(sources)                     # take the rows of these request["source"] names out of the set again
+        sess.rows(); sess.sources()               # the ledger: (source, "edit" | "retain", ordinal, token) per row; what release() can take
         sess.fold()                               # take the M preserved rows into the session's own base factor: M -> 0
         sess.folded                               # rows folded so far (still preserved, exactly)
         sess.reset()                              # forget the preserved keys (the weights stay as they are)
@@ -698,6 +725,17 @@ class EditSession:
     ``prompts`` (or ``source_prompts``) and ``source`` only.  Capacity, ``fold()`` and ``on_full`` treat retained rows like any
     other; with ``on_full="fold"`` a list longer than ``capacity`` is taken in chunks of at most ``capacity`` rows with a fold
     between chunks (the weights do not change, so every chunk sees the same keys).
+
+    RELEASE (``release``) takes named concepts out of the set again — to change an edit made twenty steps ago, whose own preserved
+    row would otherwise hold the re-edit about half-way back, or to stop holding a retained concept.  No downdating: rows below
+    the smallest released index already are the state of the reduced set, and the kept rows behind it re-enter as the key half of
+    a step on the rows the session already holds in factor coordinates (``hip.session_release``: a gather, then B, Lkp, T, its
+    Cholesky, the append) — no forward, no X, no statistics, no weight read or written; every parameter is bit-identical
+    afterwards.  Releasing only the last rows (the last step, the last retain list) or all of them launches nothing.  Rows
+    [first, M) and the touched tile inverses of every layer are copied first; all layers run, ONE pinned flag read decides, and a
+    non-zero flag puts the copy back and raises ``torch.linalg.LinAlgError`` with nothing released.  ``retained`` drops by the
+    retained rows released; a stored ``report()`` readout is dropped (``None`` until the next step).  A fold empties the ledger:
+    folded sources live inside the base factor and cannot be released (``ValueError``; ``restore()`` starts over).
 
     ``report=True`` adds one launch per edited layer to a step (``hip.session_step_norms``, from what the step left in its
     workspace: with Z = (I + Y Y^T)^-1 [0; Rt] the step moves preserved key i by dW p_i = -Zp_i and leaves Zk_j of residual j);
@@ -760,6 +798,11 @@ class EditSession:
         self.retained = 0                                    # rows added by retain(), folded ones included
         self.report_on = bool(report)
         self._report = self._report_pending = None           # (buffer (n_layers, M + 2 N) f64 in HBM, M, N, row scales) of the last sound step
+        self._ledger: List[tuple] = []                       # per live row since the last fold: (source, "edit" | "retain", ordinal, token)
+        self._folded_sources: set = set()                    # sources whose rows a fold took: no longer releasable
+        self._retains = 0                                    # retain() calls so far (the ordinal of a retained row)
+        self._release_ws: Optional[hip.ReleaseWorkspace] = None
+        self.released = 0                                    # rows released so far
 
     @property
     def preserved(self) -> int:
@@ -804,6 +847,8 @@ class EditSession:
                 f"the weights are as they were")
         self.private_factors, self._base = dst, base
         self.keys.reset()
+        self._folded_sources.update(row[0] for row in self._ledger)
+        self._ledger = []
         self.folded += M
         self.folds += 1
         LP = clip_forward.LAST_PATHS
@@ -927,6 +972,7 @@ class EditSession:
         # all edited layers together: their rows are already behind row M
         self.keys.commit(n, hip.row_scale_of(self._fixed[1], plan.cov_factors, self._fixed[0]))
         self.steps += 1
+        self._ledger += [(r.get("source"), "edit", self.steps, t) for r in requests for t in range(self._fixed[3])]
         if self._report_pending is not None:
             self._report, self._report_pending = self._report_pending, None
         if self.private_factors is None:            # the workspace this step's rows are coordinates of, and its statistics
@@ -961,6 +1007,7 @@ class EditSession:
             raise PreservedSetFull(f"{self.preserved} preserved + {n} retained concept rows exceed the session's capacity "
                                    f"{self.capacity}; open a session with a larger capacity, or with on_full='fold' (the list is "
                                    f"then taken in chunks, the set folded into the session's base factor between them)")
+        self._retains += 1
         for chunk in chunks:
             self._retain_chunk(chunk, w, shard)
         return n
@@ -1005,6 +1052,7 @@ class EditSession:
             break
         self.keys.commit(n, hip.row_scale_of(self._fixed[1], plan.cov_factors, self._fixed[0], w))
         self.retained += n
+        self._ledger += [(r.get("source"), "retain", self._retains, t) for r in requests for t in range(self._fixed[3])]
         if self.private_factors is None:
             self._shared = (plan.cov_factors, [plan.covs[l] for l in plan.layers])
         LP["session_preserved_rows"], LP["session_retained_rows"] = self.keys.M, self.retained
@@ -1012,17 +1060,81 @@ class EditSession:
         if self.verbose:
             print(f"Session retain: {n} concept rows retained at weight {w:g}, {self.keys.M} preserved")
 
+    def rows(self) -> List[tuple]:
+        """The ledger: one ``(source, "edit" | "retain", step or retain ordinal, token index)`` per preserved row, in row order since
+        the last fold."""
+        return list(self._ledger)
+
+    def sources(self) -> List[str]:
+        """The distinct sources that ``release`` can take, in the order they first entered."""
+        return list(dict.fromkeys(row[0] for row in self._ledger))
+
+    def release(self, sources, shard=None) -> int:
+        """Take every live row of ``sources`` (``request["source"]`` strings, or request dicts) out of the preserved set — all
+        ``num_edit_tokens`` rows of a request, every occurrence of a source entered more than once — so that the concept can be
+        edited again, or is no longer held (class docstring).  No weight changes.  Returns the rows released.  ``KeyError``: a source
+        without a preserved row; ``ValueError``: a folded source, an empty list, and what ``apply`` refuses; all before anything is
+        launched or allocated.  A non-positive pivot raises ``torch.linalg.LinAlgError`` with the state as it was."""
+        names = [s["source"] if isinstance(s, dict) else s for s in sources]
+        self._check_call(names or [None], shard, "a release")
+        keep, first, n_retained = release_plan(self._ledger, self._folded_sources, names)
+        M, kept = self.preserved, len(keep)
+        assert M == len(self._ledger)
+        if first < kept:                            # (trailing rows only, or every row: the set is truncated, nothing to launch)
+            self._release_rebuild(keep, first, M)
+        self.keys.release_commit(keep)
+        self._ledger = [self._ledger[i] for i in keep]
+        self.retained -= n_retained
+        self.released += M - kept
+        self._report = self._report_pending = None  # (its drift order is the old ledger's)
+        LP = clip_forward.LAST_PATHS
+        LP["session_released_rows"], LP["session_preserved_rows"], LP["session_retained_rows"] = self.released, kept, self.retained
+        if self.verbose:
+            print(f"Session release: {M - kept} rows of {len(set(names))} sources released, {kept} preserved")
+        return M - kept
+
+    def _release_rebuild(self, keep, first, M):
+        """The device half of a release: rows [first, len(keep)) of every edited layer rebuilt in place from the kept rows
+        (``hip.session_release``), ONE pinned flag read, and on a non-zero flag rows [first, M) and the touched tile inverses put back."""
+        keys, n_rebuilt = self.keys, len(keep) - first
+        dev = keys.Yp[0].device
+        ws = self._release_ws
+        if ws is None or ws.key != (n_rebuilt, keys.d, keys.capacity):
+            self._release_ws = None                 # (drop the old one first: the largest is of the order of the state itself)
+            ws = self._release_ws = hip.ReleaseWorkspace(n_rebuilt, keys.d, keys.capacity, dev)
+        keep_dev = torch.tensor(keep, dtype=torch.int32, device=dev)
+        t0, t1 = first // hip.NB, (M + hip.NB - 1) // hip.NB
+        snap = [(keys.Yp[i][first:M].clone(), keys.Lp[i][first:M].clone(), keys.tile_inv[i][t0:t1].clone())
+                for i in range(keys.n_layers)]
+        ws.info.zero_()
+        for i in range(keys.n_layers):
+            hip.session_release(keys, i, keep_dev, first, ws=ws)
+        flag = torch.empty(1, dtype=torch.int32, pin_memory=True)
+        flag.copy_(ws.info, non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()
+        code = int(flag.item())
+        if code != 0:
+            for i, (y, l, t) in enumerate(snap):
+                keys.Yp[i][first:M].copy_(y)
+                keys.Lp[i][first:M].copy_(l)
+                keys.tile_inv[i][t0:t1].copy_(t)
+            ws.info.zero_()
+            raise torch.linalg.LinAlgError(
+                f"release after step {self.steps}: the system of the {n_rebuilt} kept rows behind row {first} is not positive definite "
+                f"(non-positive pivot at column {code - 1}); the {M} preserved rows are as they were and nothing was released")
+
     def reset(self):
         """Forget the preserved keys; the weights stay as they are, the next step starts a fresh set (M = 0)."""
         if self.keys is not None:
             self.keys.reset()
         self.steps = 0
         self.private_factors = self._base = self._shared = None
-        self.folded = self.folds = self.retained = 0
+        self.folded = self.folds = self.retained = self.released = self._retains = 0
         self._report = self._report_pending = None
+        self._ledger, self._folded_sources, self._release_ws = [], set(), None
         LP = clip_forward.LAST_PATHS
         LP["session_steps"] = LP["session_preserved_rows"] = LP["session_folds"] = LP["session_folded_rows"] = 0
-        LP["session_retained_rows"] = 0
+        LP["session_retained_rows"] = LP["session_released_rows"] = 0
 
     def restore(self):
         """The edited weights back at their values of before the session's first step (bit-identical), and the keys forgotten."""

@@ -30,6 +30,7 @@ EXPORTS = [
     "emcid_edit_dual_apply_assemble_f64",
     "emcid_edit_dual_preserve_workspace_bytes", "emcid_edit_layer_dual_preserve_f64",
     "emcid_session_retain_workspace_bytes", "emcid_session_retain_f64", "emcid_session_step_norms_f64",
+    "emcid_session_release_workspace_bytes", "emcid_session_release_f64",
     "emcid_cov_factor_fold_workspace_bytes", "emcid_cov_factor_fold_f64",
     "emcid_edit_lu_workspace_bytes", "emcid_edit_layer_lu_f64", "emcid_lu_solve_f64",
     "emcid_edit_dual_cols_stage1_f64", "emcid_edit_dual_s", "emcid_edit_dual_u", "emcid_edit_dual_cols_stage2_f64",
@@ -97,6 +98,8 @@ def load():
         "emcid_session_retain_workspace_bytes": (i64, [i64, i64, i64]),
         "emcid_session_retain_f64": (i32, [p, i64, i64, f64, f64, p, i64, i64, p, i64, p, i64, p, i64, i64, p, i64, p, p]),
         "emcid_session_step_norms_f64": (i32, [p, i64, i64, i64, i64, i64, i64, p, p, p, p]),
+        "emcid_session_release_workspace_bytes": (i64, [i64, i64, i64]),
+        "emcid_session_release_f64": (i32, [p, i64, i64, i64, p, i64, p, i64, p, i64, i64, p, i64, p, p]),
         "emcid_cov_factor_fold_workspace_bytes": (i64, [i64, i64]),
         "emcid_cov_factor_fold_f64": (i32, [p, f64, p, i64, i64, i64, p, f64, f64, i32, p, i64, i64, i64, p, p, i64, p, p]),
         "emcid_cholesky_solve_f64": (i32, [p, i64, i64, p, p, p, i64, i64, p]),
@@ -1265,6 +1268,13 @@ class PreservedKeys:
         self.row_scale[self.M:self.M + int(N)] = float(scale)
         self.M += int(N)
 
+    def release_commit(self, keep):
+        """Make the rows ``keep`` (ascending indices < M) the committed set, after ``session_release`` has run on every layer and
+        the flag word read zero: compacts the host ``row_scale`` vector and sets ``M``."""
+        keep = check_keep(keep, self.M)[0]
+        self.row_scale[:len(keep)] = self.row_scale[torch.as_tensor(keep, dtype=torch.long)]
+        self.M = len(keep)
+
     def reset(self):
         self.M = 0
 
@@ -1363,6 +1373,68 @@ def session_retain(K, factors: CovFactors, layer_index: int, row_scale: float, s
         _ptr(Yp, torch.float64, "Yp"), Yp.stride(0), _ptr(Lp, torch.float64, "Lp"), Lp.stride(0), _ptr(Ti, torch.float64, "tile_inv"),
         state.capacity, state.M, _ptr(ws.buf), ws.nbytes, _ptr(ws.info, torch.int32), _stream(K)), "emcid_session_retain_f64")
     return {"ws": ws}
+
+
+class ReleaseWorkspace:
+    """HBM workspace (+ the device `info` word) of emcid_session_release_f64 for a release that rebuilds ``n_rebuilt`` rows: the
+    retain workspace of that N."""
+
+    def __init__(self, n_rebuilt: int, d: int, capacity: int, device):
+        self.key = (n_rebuilt, d, capacity)
+        self.nbytes = int(load().emcid_session_release_workspace_bytes(n_rebuilt, d, capacity))
+        if self.nbytes <= 0:
+            raise EmcidHipError(f"no release workspace for n_rebuilt={n_rebuilt}, d={d}, capacity={capacity}")
+        self.buf = torch.zeros(self.nbytes // 8, dtype=torch.float64, device=device)     # zero: the stream-K ticket counters
+        self.info = torch.zeros(1, dtype=torch.int32, device=device)
+
+
+def check_keep(keep, M: int):
+    """(keep as a list of ints, first): ``keep`` must be strictly ascending indices inside [0, M); ``first`` is the smallest index
+    that is NOT kept (== len(keep): only trailing rows go, or none).  Pure host code."""
+    keep = [int(i) for i in keep]
+    if any(i < 0 or i >= M for i in keep) or any(b <= a for a, b in zip(keep, keep[1:])):
+        raise EmcidHipError(f"keep must be strictly ascending row indices inside [0, {M})")
+    first = next((j for j, i in enumerate(keep) if i != j), len(keep))
+    return keep, first
+
+
+def session_release(state: PreservedKeys, layer_index: int, keep, first: Optional[int] = None, ws: Optional[ReleaseWorkspace] = None):
+    """Release rows of layer ``layer_index`` of ``state``: the rows ``keep`` (strictly ascending indices < ``state.M``) stay, the
+    others go.  Rows below ``first`` (the smallest released index; worked out from ``keep`` when None) are not touched; the kept
+    rows behind it are rebuilt in place as the key half of a step (include/emcid_hip.h, emcid_session_release_f64).  Nothing is
+    committed here (``state.release_commit(keep)`` after the flag word ``ws.info`` read zero, for all layers together).  A release
+    of trailing rows only, or of every row, launches nothing.  ``keep`` may be an int32 tensor on the state's device holding the
+    same indices (then ``first`` must be given and nothing is checked on the host).  Returns dict(ws | None, launched, first)."""
+    if not 0 <= layer_index < state.n_layers:
+        raise EmcidHipError(f"layer index {layer_index} outside the session state's {state.n_layers} layers")
+    Yp, Lp, Ti = state.Yp[layer_index], state.Lp[layer_index], state.tile_inv[layer_index]
+    if isinstance(keep, torch.Tensor) and keep.is_cuda:
+        if first is None:
+            raise EmcidHipError("session_release: a device tensor of kept rows needs `first`")
+        keep_dev, n_keep, first = keep, int(keep.numel()), int(first)
+        if keep_dev.dtype != torch.int32 or not keep_dev.is_contiguous() or keep_dev.device != Yp.device:
+            raise EmcidHipError(f"session_release: keep must be a contiguous int32 tensor on {Yp.device}")
+    else:
+        rows, f = check_keep(keep.tolist() if isinstance(keep, torch.Tensor) else keep, state.M)
+        if first is not None and int(first) != f:
+            raise EmcidHipError(f"session_release: first = {first}, but the smallest released row of keep is {f}")
+        keep_dev, n_keep, first = None, len(rows), f
+    if not 0 <= first <= n_keep <= state.M:
+        raise EmcidHipError(f"session_release: first = {first}, {n_keep} kept rows, {state.M} committed")
+    if n_keep == state.M or first == n_keep:       # nothing goes; or only trailing rows (everything included): the set is truncated
+        return {"ws": None, "launched": False, "first": first}
+    if keep_dev is None:
+        keep_dev = torch.tensor(rows, dtype=torch.int32, device=Yp.device)
+    n_rebuilt = n_keep - first
+    if ws is None or ws.key != (n_rebuilt, state.d, state.capacity):
+        ws = ReleaseWorkspace(n_rebuilt, state.d, state.capacity, Yp.device)
+    for t, nm in ((Yp, "Yp"), (Lp, "Lp"), (Ti, "tile_inv")):
+        assert t.stride(-1) == 1 and (t.dim() < 3 or t.is_contiguous()), nm
+    _check(load().emcid_session_release_f64(
+        _ptr(keep_dev, torch.int32, "keep"), n_keep, first, state.d, _ptr(Yp, torch.float64, "Yp"), Yp.stride(0),
+        _ptr(Lp, torch.float64, "Lp"), Lp.stride(0), _ptr(Ti, torch.float64, "tile_inv"), state.capacity, state.M,
+        _ptr(ws.buf), ws.nbytes, _ptr(ws.info, torch.int32), _stream(Yp)), "emcid_session_release_f64")
+    return {"ws": ws, "launched": True, "first": first}
 
 
 def session_step_norms(ws: PreserveWorkspace, N: int, d: int, h: int, state: PreservedKeys, out: Optional[torch.Tensor] = None):

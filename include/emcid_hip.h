@@ -412,6 +412,24 @@ int emcid_session_retain_f64(const float* K, int64_t N, int64_t d, double row_sc
                              double* tile_inv, int64_t capacity, int64_t M, void* workspace, int64_t workspace_bytes, int* info_dev,
                              void* stream);
 
+/* RELEASE rows of a preserved key set (edit sessions: a concept that is to be re-edited, or no longer held; entry points added
+ * under ABI 16).  No downdating: with keep_dev [n_keep] the ascending indices (< M) of the rows that stay and `first` the smallest
+ * released index (keep[j] == j for j < first), rows < first of Yp and Lp and the leading parts of the tile inverses already are
+ * the state of the reduced set.  The kept rows behind `first` are gathered (through the workspace: source and destination overlap
+ * in Yp) and re-enter as the key half of the step above with M = first, N = n_keep - first, Yk = those rows:
+ *     B = Yk Yp^T,  Lkp = B Lp^-T,  T = I + Yk Yk^T - Lkp Lkp^T = Lkk Lkk^T,  append [Lkp Lkk],  extend the tile inverses
+ * — no forward, no X, no statistics, no weights; O(N n_keep d + N^3 / 3).  ONE layer per call, no host synchronisation.  Rows
+ * < first of Yp and Lp and the tiles wholly below `first` are never written; rows [first, n_keep) are rewritten in place (rows
+ * >= n_keep are left as they were and no longer count); info_dev reports a non-positive pivot of T as the retain entry does, and
+ * the caller then puts its copy of rows [first, M) back.  Needs 0 <= first < n_keep < M <= capacity: a release of trailing rows
+ * only (first == n_keep) or of every row (n_keep == 0) is the caller passing a smaller M next time, no call.  An index of
+ * keep_dev outside [0, M) reads nothing (its row enters as zeros).  workspace: emcid_session_release_workspace_bytes(n_rebuilt
+ * = n_keep - first, d, capacity), the retain workspace of that N (0 for n_rebuilt <= 0 or > capacity). */
+int64_t emcid_session_release_workspace_bytes(int64_t n_rebuilt, int64_t d, int64_t capacity);
+int emcid_session_release_f64(const int32_t* keep_dev, int64_t n_keep, int64_t first, int64_t d, double* Yp, int64_t ldy, double* Lp,
+                              int64_t ldl, double* tile_inv, int64_t capacity, int64_t M, void* workspace, int64_t workspace_bytes,
+                              int* info_dev, void* stream);
+
 /* The readout of a preserve step, from what it left in its workspace.  With Z = (I + Y Y^T)^-1 [0; Rt] (Y = [Yp; Yk]) the step
  * moves every preserved key by dW p_i = -Zp_i and leaves Zk_j of each new residual; ZT = [Zp^T | Zk^T] and Rt are still in the
  * workspace when the step returns.  Called stream-ordered right after emcid_edit_layer_dual_preserve_f64 on the SAME workspace
