@@ -1788,6 +1788,12 @@ static void trsm_tiles_backward(const double* Lp, int64_t ldl, const double* tin
     }
 }
 
+// the blocks of a workspace that the key half of a step works on (session_append_rows)
+struct KeyHalf {
+    double *Yt, *S, *LS, *invS, *XT, *TT, *B;
+    int64_t dp, Np, cp;
+};
+
 struct PreserveWorkspace {
     DualWorkspace dual;
     int64_t cp, off_B, off_ZT, off_G, total;   // doubles
@@ -1798,6 +1804,10 @@ struct PreserveWorkspace {
         off_ZT = o; o += dual.hp * cp;       // [Zp^T | Zk^T]
         off_G = o; o += dual.hp * cp;        // -(Zk^T Lkp), consumed by the backward solve
         total = o;
+    }
+    KeyHalf key_half(double* base) const {
+        return {base + dual.off_Y, base + dual.off_S, base + dual.off_LS, base + dual.off_invS, base + dual.off_XT, base + dual.off_TT,
+                base + off_B, dual.dp, dual.Np, cp};
     }
 };
 
@@ -1821,7 +1831,81 @@ struct RetainWorkspace {
         off_B = o; o += Np * cp;
         total = o;
     }
+    KeyHalf key_half(double* base) const {
+        return {base + off_Y, base + off_S, base + off_LS, base + off_invS, base + off_XT, base + off_TT, base + off_B, dp, Np, cp};
+    }
 };
+
+// what the session entries ask of the caller's state (Yp, Lp, tile inverses) for N rows behind row M
+static bool session_state_ok(int64_t M, int64_t N, int64_t d, const double* Yp, int64_t ldy, const double* Lp, int64_t ldl,
+                             const double* tile_inv, int64_t capacity) {
+    return M >= 0 && M + N <= capacity && capacity < (int64_t)1 << 30 && ldy >= round_up(d, NB) && ldy % 2 == 0 && ldl >= capacity &&
+           ldl % 2 == 0 && aligned16(Yp) && aligned16(Lp) && aligned16(tile_inv);
+}
+
+// The key half of a step behind row M, from N rows that already are in factor coordinates (k.Yt [Np][dp]): the copy into Yp,
+// B = Yk Yp^T, Lkp = B Lp^-T, T = I + Yk Yk^T - Lkp Lkp^T, its Cholesky (the explicit inverse XS = inv(LS) riding in the
+// factorization's launches as an XrowJob, transposed, when the fused schedule runs), the append and the tile inverses.  A preserve
+// step, a retain list and a release all run it.
+static int session_append_rows(const KeyHalf& k, int64_t N, double* Yp, int64_t ldy, double* Lp, int64_t ldl, double* tile_inv,
+                               int64_t M, int* info_dev, hipStream_t st, const char* who) {
+    const int64_t dp = k.dp, Np = k.Np, cp = k.cp;
+    double* Yk = Yp + M * ldy;
+    double* Lkp = Lp + M * ldl;
+    hipLaunchKernelGGL(copy2d_f64_kernel, dim3((unsigned)N), dim3(256), 0, st, k.Yt, dp, Yk, ldy, (int)N, (int)dp, 1.0);
+    if (M > 0) {
+        // B = Yk Yp^T: few output tiles, dp deep — the contraction is split, the partials added into zeros
+        hipLaunchKernelGGL(zero2d_f64_kernel, dim3((unsigned)N, 1u), dim3(256), 0, st, k.B, cp, (int64_t)0, (int)M);
+        {
+            ScopedProf sp(KC_ASSEMBLE, st);
+            GemmShape g{Yk, ldy, Yp, ldy, (int)N, (int)M, (int)dp, 0};
+            launch_gemm_f64<true, true>(g, EpiAxpby{k.B, cp, 1.0, 1.0}, st);
+        }
+        trsm_tiles_forward(Lp, ldl, tile_inv, M, k.B, cp, Lkp, ldl, (int)N, st);
+    }
+    assemble_schur_system(Yk, ldy, dp, Lkp, ldl, M, k.S, (int)N, (int)Np, st);
+    const XrowJob xj{k.XT, Np, k.TT};
+    EMCID_TRY(cholesky_impl(k.S, k.LS, Np, Np, k.invS, info_dev, st, nullptr, cholesky_takes_shadow(Np) ? &xj : nullptr));
+    hipLaunchKernelGGL(append_factor_kernel, dim3((unsigned)N), dim3(256), 0, st, k.LS, Np, Lp, ldl, (int)M, (int)N);
+    {
+        ScopedProf sp(KC_INV_BLOCK, st);
+        const unsigned tiles = (unsigned)((M + N - 1) / NB - M / NB + 1);
+        hipLaunchKernelGGL(tile_inverse_extend_kernel, dim3(tiles, NB / 16), dim3(64), 0, st, Lp, ldl, tile_inv, (int)M, (int)(M + N));
+    }
+    return check_launch(who);
+}
+
+// RT[h, Np] = Rt^T, then RT := Z^T = RT S^-1 for S = LS LS^T (Y2 [h, Np] is scratch).  As block substitution the solve is 6
+// dependent launches on h rows (~140 us at N = 1000, latency-bound); against an explicit XS = inv(LS) it is two GEMMs against a
+// triangle, Z^T = (RT XS^T) XS.  XT: XS transposed, as it rode in the factorization (XrowJob), or nullptr when the fused schedule
+// did not run.  Then XS is built into `full_inv` [Np, Np] (the callers pass S, which the factorization has consumed) up to
+// Np = 4096; beyond that, or without `full_inv`, the substitution stays.
+static int solve_schur_rhs(const double* R, int64_t hp, int64_t h, int64_t Np, const double* LS, const double* invS, const double* XT,
+                           double* full_inv, double* RT, double* Y2, hipStream_t st) {
+    hipLaunchKernelGGL(transpose_f64_kernel, dim3((unsigned)((hp + 31) / 32), (unsigned)(Np / 32)), dim3(256), 0, st, R, hp, RT, Np,
+                       (int)Np, (int)hp);
+    if (XT) {
+        ScopedProf sp(KC_TRSM_DIAG, st);
+        GemmShape f{RT, Np, XT, Np, (int)h, (int)Np, (int)Np, 0};
+        f.tri = 1; f.pair = 1;       // B(k, n) = XS[n][k] = Xt[k][n], zero for k > n
+        launch_gemm_f64<true, false>(f, EpiAxpby{Y2, Np, 1.0, 0.0}, st);
+        GemmShape b{Y2, Np, XT, Np, (int)h, (int)Np, (int)Np, 0};
+        b.tri = 2; b.pair = 1;       // B(k, n) = XS[k][n] = Xt[n][k], zero for k < n
+        launch_gemm_f64<true, true>(b, EpiAxpby{RT, Np, 1.0, 0.0}, st);
+    } else if (full_inv && Np <= 4096) {
+        EMCID_TRY(build_full_inverse(LS, Np, Np, invS, full_inv, Y2, 1, 0, 0, st));
+        ScopedProf sp(KC_TRSM_DIAG, st);
+        GemmShape f{RT, Np, full_inv, Np, (int)h, (int)Np, (int)Np, 0};
+        f.tri = 1; f.pair = 1;       // B(k, n) = XS[n][k], zero for k > n
+        launch_gemm_f64<true, true>(f, EpiAxpby{Y2, Np, 1.0, 0.0}, st);
+        GemmShape b{Y2, Np, full_inv, Np, (int)h, (int)Np, (int)Np, 0};
+        b.tri = 2; b.pair = 1;       // B(k, n) = XS[k][n], zero for k < n
+        launch_gemm_f64<true, false>(b, EpiAxpby{RT, Np, 1.0, 0.0}, st);
+    } else {
+        EMCID_TRY(cholesky_solve_impl(LS, Np, Np, invS, RT, Y2, h, Np, st));
+    }
+    return EMCID_OK;
+}
 
 }  // namespace emcid
 
@@ -2517,35 +2601,7 @@ int emcid_edit_dual_apply_stage2_f64(int64_t N, int64_t d, int64_t h, const void
         const XrowJob xj{XT, Np, TT};
         EMCID_TRY(cholesky_impl(S, LS, Np, Np, invS, info_dev, q, shadow ? &job : nullptr, xrow ? &xj : nullptr));
         // RT[h, Np] = Rt^T ; Z^T = RT S^-1 (two solves with h rows)
-        hipLaunchKernelGGL(transpose_f64_kernel, dim3((unsigned)((hp + 31) / 32), (unsigned)(Np / 32)), dim3(256), 0, q, R, hp, RT,
-                           Np, (int)Np, (int)hp);
-        // Z^T = RT S^-1.  As block substitution this is 6 dependent launches on h rows (~140 us at N = 1000, latency-bound); with
-        // XS = inv(LS) made explicit (one more halving level on top of the 512-block inverses, into S, which the factorization has
-        // consumed) it is two GEMMs against a triangle:  Z^T = (RT XS^T) XS (the substitution stays for N the fused schedule does not take).
-        if (xrow) {
-            ScopedProf sp(KC_TRSM_DIAG, q);
-            GemmShape f{RT, Np, XT, Np, (int)h, (int)Np, (int)Np, 0};
-            f.tri = 1;       // B(k, n) = XS[n][k] = Xt[k][n], zero for k > n
-            f.pair = 1;
-            launch_gemm_f64<true, false>(f, EpiAxpby{Y2, Np, 1.0, 0.0}, q);
-            GemmShape b{Y2, Np, XT, Np, (int)h, (int)Np, (int)Np, 0};
-            b.tri = 2;       // B(k, n) = XS[k][n] = Xt[n][k], zero for k < n
-            b.pair = 1;
-            launch_gemm_f64<true, true>(b, EpiAxpby{RT, Np, 1.0, 0.0}, q);
-        } else if (Np <= 4096) {
-            EMCID_TRY(build_full_inverse(LS, Np, Np, invS, S, Y2, 1, 0, 0, q));
-            ScopedProf sp(KC_TRSM_DIAG, q);
-            GemmShape f{RT, Np, S, Np, (int)h, (int)Np, (int)Np, 0};
-            f.tri = 1;       // B(k, n) = XS[n][k], zero for k > n
-            f.pair = 1;
-            launch_gemm_f64<true, true>(f, EpiAxpby{Y2, Np, 1.0, 0.0}, q);
-            GemmShape b{Y2, Np, S, Np, (int)h, (int)Np, (int)Np, 0};
-            b.tri = 2;       // B(k, n) = XS[k][n], zero for k < n
-            b.pair = 1;
-            launch_gemm_f64<true, false>(b, EpiAxpby{RT, Np, 1.0, 0.0}, q);
-        } else {
-            EMCID_TRY(cholesky_solve_impl(LS, Np, Np, invS, RT, Y2, h, Np, q));
-        }
+        EMCID_TRY(solve_schur_rhs(R, hp, h, Np, LS, invS, xrow ? XT : nullptr, S, RT, Y2, q));
         if (!shadow && !p_first) {
             ScopedProf sp(KC_DELTA_W, q);       // V[h, dp] = Z^T Yt
             GemmShape g{RT, Np, Yt, dp, (int)h, (int)dp, (int)Np, 0};
@@ -2588,72 +2644,23 @@ int emcid_edit_layer_dual_preserve_f64(const float* K, const float* Zc, const fl
                                        double* U_out, void* workspace, int64_t workspace_bytes, int* info_dev, void* stream) {
     EMCID_CHECK_ARG(N > 0 && d > 0 && h > 0 && Yp && Lp && tile_inv && workspace && info_dev && cov_factor_ws);
     EMCID_CHECK_ARG(0 <= layer_index && layer_index < n_layers && (W || dW_out || U_out) && ((W == nullptr) || (W0 != nullptr)));
-    EMCID_CHECK_ARG(M >= 0 && M + N <= capacity && capacity < (int64_t)1 << 30);
+    EMCID_CHECK_ARG(session_state_ok(M, N, d, Yp, ldy, Lp, ldl, tile_inv, capacity));
     PreserveWorkspace pw(N, d, h, capacity);
     const DualWorkspace& ws = pw.dual;
-    EMCID_CHECK_ARG(ldy >= ws.dp && ldy % 2 == 0 && ldl >= capacity && ldl % 2 == 0 && aligned16(Yp) && aligned16(Lp) && aligned16(tile_inv));
     if (workspace_bytes < pw.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     // Kt64, Rt and Yt = Kt64 X^T, exactly as the plain apply-only form
     EMCID_TRY(emcid_edit_dual_apply_stage1_f64(K, Zc, zs_t, N, d, h, edit_weight, layers_left, lam_ratio, cov_factor_ws, n_layers,
                                                layer_index, 0, N, 1, workspace, ws.total * (int64_t)sizeof(double), stream));
     double* base = (double*)workspace;
-    double *Yt = base + ws.off_Y, *R = base + ws.off_R, *S = base + ws.off_S, *LS = base + ws.off_LS, *invS = base + ws.off_invS;
-    double *RT = base + ws.off_PT, *Y2 = base + ws.off_Y2, *V = base + ws.off_V, *U = base + ws.off_U;
-    double *XT = base + ws.off_XT, *TT = base + ws.off_TT;
-    double *Bw = base + pw.off_B, *ZT = base + pw.off_ZT, *G = base + pw.off_G;
-    const int64_t dp = ws.dp, Np = ws.Np, hp = ws.hp, cp = pw.cp;
-    double* Yk = Yp + M * ldy;
+    const KeyHalf k = pw.key_half(base);
+    double *R = base + ws.off_R, *RT = base + ws.off_PT, *Y2 = base + ws.off_Y2, *V = base + ws.off_V, *U = base + ws.off_U;
+    double *ZT = base + pw.off_ZT, *G = base + pw.off_G;
+    const int64_t dp = ws.dp, Np = ws.Np, cp = pw.cp;
     double* Lkp = Lp + M * ldl;
-    hipLaunchKernelGGL(copy2d_f64_kernel, dim3((unsigned)N), dim3(256), 0, st, Yt, dp, Yk, ldy, (int)N, (int)dp, 1.0);
-    if (M > 0) {
-        // B = Yk Yp^T: few output tiles, dp deep — the contraction is split, the partials added into zeros
-        hipLaunchKernelGGL(zero2d_f64_kernel, dim3((unsigned)N, 1u), dim3(256), 0, st, Bw, cp, (int64_t)0, (int)M);
-        {
-            ScopedProf sp(KC_ASSEMBLE, st);
-            GemmShape g{Yk, ldy, Yp, ldy, (int)N, (int)M, (int)dp, 0};
-            launch_gemm_f64<true, true>(g, EpiAxpby{Bw, cp, 1.0, 1.0}, st);
-        }
-        trsm_tiles_forward(Lp, ldl, tile_inv, M, Bw, cp, Lkp, ldl, (int)N, st);
-    }
-    assemble_schur_system(Yk, ldy, dp, Lkp, ldl, M, S, (int)N, (int)Np, st);
-    const bool xrow = cholesky_takes_shadow(Np);
-    const XrowJob xj{XT, Np, TT};
-    EMCID_TRY(cholesky_impl(S, LS, Np, Np, invS, info_dev, st, nullptr, xrow ? &xj : nullptr));
-    hipLaunchKernelGGL(append_factor_kernel, dim3((unsigned)N), dim3(256), 0, st, LS, Np, Lp, ldl, (int)M, (int)N);
-    {
-        ScopedProf sp(KC_INV_BLOCK, st);
-        const unsigned tiles = (unsigned)((M + N - 1) / NB - M / NB + 1);
-        hipLaunchKernelGGL(tile_inverse_extend_kernel, dim3(tiles, NB / 16), dim3(64), 0, st, Lp, ldl, tile_inv, (int)M, (int)(M + N));
-    }
-    // RT[h, Np] = Rt^T ; Zk^T = RT T^-1 (as emcid_edit_dual_apply_stage2_f64)
-    hipLaunchKernelGGL(transpose_f64_kernel, dim3((unsigned)((hp + 31) / 32), (unsigned)(Np / 32)), dim3(256), 0, st, R, hp, RT, Np,
-                       (int)Np, (int)hp);
-    if (xrow) {
-        ScopedProf sp(KC_TRSM_DIAG, st);
-        GemmShape f{RT, Np, XT, Np, (int)h, (int)Np, (int)Np, 0};
-        f.tri = 1;
-        f.pair = 1;
-        launch_gemm_f64<true, false>(f, EpiAxpby{Y2, Np, 1.0, 0.0}, st);
-        GemmShape b{Y2, Np, XT, Np, (int)h, (int)Np, (int)Np, 0};
-        b.tri = 2;
-        b.pair = 1;
-        launch_gemm_f64<true, true>(b, EpiAxpby{RT, Np, 1.0, 0.0}, st);
-    } else if (Np <= 4096) {
-        // (S has been consumed by the factorization: the explicit inverse of LS goes there)
-        EMCID_TRY(build_full_inverse(LS, Np, Np, invS, S, Y2, 1, 0, 0, st));
-        ScopedProf sp(KC_TRSM_DIAG, st);
-        GemmShape f{RT, Np, S, Np, (int)h, (int)Np, (int)Np, 0};
-        f.tri = 1;
-        f.pair = 1;
-        launch_gemm_f64<true, true>(f, EpiAxpby{Y2, Np, 1.0, 0.0}, st);
-        GemmShape b{Y2, Np, S, Np, (int)h, (int)Np, (int)Np, 0};
-        b.tri = 2;
-        b.pair = 1;
-        launch_gemm_f64<true, false>(b, EpiAxpby{RT, Np, 1.0, 0.0}, st);
-    } else {
-        EMCID_TRY(cholesky_solve_impl(LS, Np, Np, invS, RT, Y2, h, Np, st));
-    }
+    EMCID_TRY(session_append_rows(k, N, Yp, ldy, Lp, ldl, tile_inv, M, info_dev, st, __func__));
+    // RT[h, Np] = Rt^T ; Zk^T = RT T^-1
+    EMCID_TRY(solve_schur_rhs(R, ws.hp, h, Np, k.LS, k.invS, cholesky_takes_shadow(Np) ? k.XT : nullptr, k.S, RT, Y2, st));
     // ZT = [Zp^T | Zk^T] [h, M + N]: then V = ZT [Yp; Yk] is ONE product over the state's rows, the new ones included
     hipLaunchKernelGGL(copy2d_f64_kernel, dim3((unsigned)h), dim3(256), 0, st, RT, Np, ZT + M, cp, (int)h, (int)N, 1.0);
     if (M > 0) {
@@ -2676,40 +2683,6 @@ int emcid_edit_layer_dual_preserve_f64(const float* K, const float* Zc, const fl
     return EMCID_OK;
 }
 
-// The key half of a step behind row M, from N rows that already are in factor coordinates (Yt [Np][dp] in the workspace): the
-// copy into Yp, B, Lkp, T, its Cholesky (the explicit inverse riding in it as in a preserve step), the append and the tile
-// inverses.  emcid_session_retain_f64 and emcid_session_release_f64 both end in it.
-static int session_append_rows(const RetainWorkspace& ws, double* base, int64_t N, double* Yp, int64_t ldy, double* Lp, int64_t ldl,
-                               double* tile_inv, int64_t M, int* info_dev, hipStream_t st, const char* who) {
-    double *Yt = base + ws.off_Y, *S = base + ws.off_S, *LS = base + ws.off_LS, *invS = base + ws.off_invS;
-    double *XT = base + ws.off_XT, *TT = base + ws.off_TT, *Bw = base + ws.off_B;
-    const int64_t dp = ws.dp, Np = ws.Np, cp = ws.cp;
-    double* Yk = Yp + M * ldy;
-    double* Lkp = Lp + M * ldl;
-    hipLaunchKernelGGL(copy2d_f64_kernel, dim3((unsigned)N), dim3(256), 0, st, Yt, dp, Yk, ldy, (int)N, (int)dp, 1.0);
-    if (M > 0) {
-        hipLaunchKernelGGL(zero2d_f64_kernel, dim3((unsigned)N, 1u), dim3(256), 0, st, Bw, cp, (int64_t)0, (int)M);
-        {
-            ScopedProf sp(KC_ASSEMBLE, st);      // B = Yk Yp^T
-            GemmShape g{Yk, ldy, Yp, ldy, (int)N, (int)M, (int)dp, 0};
-            launch_gemm_f64<true, true>(g, EpiAxpby{Bw, cp, 1.0, 1.0}, st);
-        }
-        trsm_tiles_forward(Lp, ldl, tile_inv, M, Bw, cp, Lkp, ldl, (int)N, st);
-    }
-    assemble_schur_system(Yk, ldy, dp, Lkp, ldl, M, S, (int)N, (int)Np, st);
-    // (the factorization's launches are those of a preserve step, the explicit inverse of LS riding in them included)
-    const bool xrow = cholesky_takes_shadow(Np);
-    const XrowJob xj{XT, Np, TT};
-    EMCID_TRY(cholesky_impl(S, LS, Np, Np, invS, info_dev, st, nullptr, xrow ? &xj : nullptr));
-    hipLaunchKernelGGL(append_factor_kernel, dim3((unsigned)N), dim3(256), 0, st, LS, Np, Lp, ldl, (int)M, (int)N);
-    {
-        ScopedProf sp(KC_INV_BLOCK, st);
-        const unsigned tiles = (unsigned)((M + N - 1) / NB - M / NB + 1);
-        hipLaunchKernelGGL(tile_inverse_extend_kernel, dim3(tiles, NB / 16), dim3(64), 0, st, Lp, ldl, tile_inv, (int)M, (int)(M + N));
-    }
-    return check_launch(who);
-}
-
 /* ---- edit sessions: a RETAIN list — preserved rows with a zero residual -------------------------------------------------------
  * The first half of emcid_edit_layer_dual_preserve_f64 for keys that are to stay where they are: Yk, B, Lkp, T, its Cholesky and
  * the append behind row M.  With Rt = 0 the step's Zk, Zp and U vanish identically, so that half is not run at all: no Zc, no
@@ -2726,9 +2699,8 @@ int emcid_session_retain_f64(const float* K, int64_t N, int64_t d, double row_sc
     EMCID_CHECK_ARG(K && N > 0 && d > 0 && Yp && Lp && tile_inv && workspace && info_dev && cov_factor_ws);
     EMCID_CHECK_ARG(0 <= layer_index && layer_index < n_layers && row_scale > 0.0 && row_scale < 1e150);
     EMCID_CHECK_ARG(lam_ratio > 0.0 && lam_ratio < 1e300);
-    EMCID_CHECK_ARG(M >= 0 && M + N <= capacity && capacity < (int64_t)1 << 30);
+    EMCID_CHECK_ARG(session_state_ok(M, N, d, Yp, ldy, Lp, ldl, tile_inv, capacity));
     RetainWorkspace ws(N, d, capacity);
-    EMCID_CHECK_ARG(ldy >= ws.dp && ldy % 2 == 0 && ldl >= capacity && ldl % 2 == 0 && aligned16(Yp) && aligned16(Lp) && aligned16(tile_inv));
     if (workspace_bytes < ws.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     double* base = (double*)workspace;
@@ -2741,7 +2713,7 @@ int emcid_session_retain_f64(const float* K, int64_t N, int64_t d, double row_sc
     }
     // Yt = Kt64 X^T over the Np padded rows, as stage 1 of the apply-only form runs the whole concept range
     apply_inverse_forward(cov_inverse(cov_factor_ws, n_layers, dp, layer_index), dp, Kt, Yt, (int)Np, st, base + ws.off_SK);
-    return session_append_rows(ws, base, N, Yp, ldy, Lp, ldl, tile_inv, M, info_dev, st, __func__);
+    return session_append_rows(ws.key_half(base), N, Yp, ldy, Lp, ldl, tile_inv, M, info_dev, st, __func__);
 }
 
 /* ---- edit sessions: RELEASE rows of the preserved set ----------------------------------------------------------------------------
@@ -2757,16 +2729,16 @@ int emcid_session_release_f64(const int32_t* keep_dev, int64_t n_keep, int64_t f
                               int64_t ldl, double* tile_inv, int64_t capacity, int64_t M, void* workspace, int64_t workspace_bytes,
                               int* info_dev, void* stream) {
     EMCID_CHECK_ARG(keep_dev && d > 0 && Yp && Lp && tile_inv && workspace && aligned16(workspace) && info_dev);
-    EMCID_CHECK_ARG(first >= 0 && first < n_keep && n_keep < M && M <= capacity && capacity < (int64_t)1 << 30);
+    EMCID_CHECK_ARG(first < n_keep && n_keep < M && M <= capacity);
     const int64_t N = n_keep - first;
+    EMCID_CHECK_ARG(session_state_ok(first, N, d, Yp, ldy, Lp, ldl, tile_inv, capacity));
     RetainWorkspace ws(N, d, capacity);
-    EMCID_CHECK_ARG(ldy >= ws.dp && ldy % 2 == 0 && ldl >= capacity && ldl % 2 == 0 && aligned16(Yp) && aligned16(Lp) && aligned16(tile_inv));
     if (workspace_bytes < ws.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     double* base = (double*)workspace;
     hipLaunchKernelGGL(gather_rows_f64_kernel, dim3((unsigned)ws.Np), dim3(256), 0, st, Yp, ldy, keep_dev + first, (int)N, (int)M,
                        base + ws.off_Y, (int)ws.dp);
-    return session_append_rows(ws, base, N, Yp, ldy, Lp, ldl, tile_inv, first, info_dev, st, __func__);
+    return session_append_rows(ws.key_half(base), N, Yp, ldy, Lp, ldl, tile_inv, first, info_dev, st, __func__);
 }
 
 /* The readout of the preserve step that has just run on `workspace` (same N, d, h, capacity, M, same stream): the step left
@@ -2874,21 +2846,8 @@ int emcid_edit_dual_cols_stage2_f64(int64_t N, int64_t d, int64_t h, const void*
         hipLaunchKernelGGL(add_identity_f64_kernel, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, q, S, (int)Np);
         const XrowJob xj{base + ws.off_XT, Np, base + ws.off_TT};
         EMCID_TRY(cholesky_impl(S, LS, Np, Np, invS, info_dev, q, nullptr, xrow ? &xj : nullptr));
-        hipLaunchKernelGGL(transpose_f64_kernel, dim3((unsigned)((hp + 31) / 32), (unsigned)(Np / 32)), dim3(256), 0, q, R, hp, RT,
-                           Np, (int)Np, (int)hp);
-        if (xrow) {     // Z^T = (RT XS^T) XS against the inverse that rode in the factorization (as emcid_edit_dual_apply_stage2_f64)
-            ScopedProf sp(KC_TRSM_DIAG, q);
-            GemmShape f{RT, Np, xj.Xt, Np, (int)h, (int)Np, (int)Np, 0};
-            f.tri = 1;
-            f.pair = 1;
-            launch_gemm_f64<true, false>(f, EpiAxpby{Y2, Np, 1.0, 0.0}, q);
-            GemmShape b{Y2, Np, xj.Xt, Np, (int)h, (int)Np, (int)Np, 0};
-            b.tri = 2;
-            b.pair = 1;
-            launch_gemm_f64<true, true>(b, EpiAxpby{RT, Np, 1.0, 0.0}, q);
-        } else {
-            EMCID_TRY(cholesky_solve_impl(LS, Np, Np, invS, RT, Y2, h, Np, q));      // RT := Z^T
-        }
+        // RT := Z^T, against the inverse that rode in the factorization or by substitution
+        EMCID_TRY(solve_schur_rhs(R, hp, h, Np, LS, invS, xrow ? xj.Xt : nullptr, nullptr, RT, Y2, q));
         {
             ScopedProf sp(KC_DELTA_W, q);       // V[h, w] = Z^T Yc
             GemmShape g{RT, Np, Yc, dp, (int)h, w, (int)Np, 0};

@@ -586,11 +586,17 @@ def _any_rank(flag: bool, device) -> bool:
     return bool(int(t.item()))
 
 
+def _note_stale(who: str, e, what: str = "call"):
+    """Before a call is repeated after ``StaleWeightCacheError``: say so and drop the forward's weight-derived caches."""
+    logging.getLogger("emcid_amd").warning("%s: %s; redoing the %s from the live weights", who, e, what)
+    clip_forward.invalidate_weight_caches(None)
+
+
 def _retry_if_stale(fn):
     """The forward's weight-derived caches carry a content guard (clip_forward.WeightGuard): when an edit finds that a weight was
     rewritten behind them (``param.data.copy_(...)`` between two calls), the engine puts the edited weights back, drops the caches
     and raises ``StaleWeightCacheError`` — the call is redone once, from the live weights.  A multi-rank job raises instead: one
-    rank redoing its call alone would leave the others inside their collectives."""
+    rank repeating its call alone would leave the others inside their collectives."""
     @functools.wraps(fn)
     def wrapper(*args, **kwargs):
         try:
@@ -599,8 +605,7 @@ def _retry_if_stale(fn):
             import torch.distributed as dist
             if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
                 raise
-            logging.getLogger("emcid_amd").warning("%s: %s; redoing the call from the live weights", fn.__name__, e)
-            clip_forward.invalidate_weight_caches(None)
+            _note_stale(fn.__name__, e)
             clip_forward.LAST_PATHS["stale_cache_retries"] = clip_forward.LAST_PATHS.get("stale_cache_retries", 0) + 1
             return fn(*args, **kwargs)
     return wrapper
@@ -832,10 +837,7 @@ class EditSession:
         ws = torch.empty(M * dst.dp, dtype=torch.float64, device=dev)
         for i in range(len(layers)):
             hip.cov_factor_fold(src, self.keys, i, self._shared[1][i] if first else None, lam, e, dst, base, ws=ws)
-        flag = torch.empty(1, dtype=torch.int32, pin_memory=True)
-        flag.copy_(dst.info, non_blocking=True)
-        torch.cuda.current_stream(dev).synchronize()
-        code = int(flag.item())
+        code = self._read_flag(dst.info)
         if code != 0:
             if keep is not None:
                 dst.buf.copy_(keep[0])
@@ -919,6 +921,58 @@ class EditSession:
         return {l: nethook.get_parameter(self.pipe.text_encoder, f"{self.hparams.rewrite_module_tmp.format(l)}.weight")
                 for l in self._fixed[2]}
 
+    def _ensure_keys(self):
+        """Allocate the preserved key set at the first step or retain list, on the encoder's device (HBM only)."""
+        if self.keys is None:
+            w = next(iter(self._weights().values()))
+            if not w.is_cuda:
+                raise hip.EmcidHipError(f"the text encoder must live in HBM (got {w.device}); there is no CPU path")
+            self.keys = hip.PreservedKeys(len(self._fixed[2]), self.d, self.capacity, w.device)
+
+    @staticmethod
+    def _read_flag(info: torch.Tensor) -> int:
+        """The ONE synchronising read of an operation: the device flag word ``info`` through a pinned word, after everything
+        queued on the current stream of its device."""
+        flag = torch.empty(1, dtype=torch.int32, pin_memory=True)
+        flag.copy_(info, non_blocking=True)
+        torch.cuda.current_stream(info.device).synchronize()
+        return int(flag.item())
+
+    def _run_plan(self, make_plan, restore_weights: bool, method: str, redo: str, keys: str, where: str, undone: str = ""):
+        """Run the plan ``make_plan()`` returns as this session's and return it once every factorization was sound; nothing is
+        committed here.  Any failure releases the plan's workspaces (``restore_weights``: and puts the edited weights back); a
+        weight rewritten behind the forward's caches (``StaleWeightCacheError``) has the plan made and run again once, from the live
+        weights, M unchanged; a non-positive pivot becomes ``torch.linalg.LinAlgError``.  The other arguments word the messages."""
+        LP = clip_forward.LAST_PATHS
+        for attempt in (0, 1):
+            plan = make_plan()
+            plan.session = self
+            stats_flag = None
+            self._report_pending = None
+            try:
+                try:
+                    with phase("run + final sync"):
+                        run_encoder_edit(plan, keep_factors=False, restore=False)
+                except BaseException:
+                    if restore_weights:
+                        plan.restore_weights()
+                    edit_engine._release_workspaces(plan)
+                    raise
+                # (check_info drops a failed plan's own factors: keep their flag word to tell which factorization said no)
+                stats_flag = plan.cov_factors.info if plan.cov_factors is not None else None
+                check_info(plan)                    # restores the weights itself before it raises
+                return plan
+            except clip_forward.StaleWeightCacheError as e:
+                if attempt == 1:
+                    raise
+                _note_stale(f"EditSession.{method}", e, redo)
+                LP["stale_cache_retries"] = LP.get("stale_cache_retries", 0) + 1
+            except FloatingPointError as e:
+                what = "the statistics lam C' themselves are not positive definite" if stats_flag is not None and int(stats_flag.item()) \
+                    else f"the system of the {keys} keys given the {self.preserved} preserved ones is not positive definite"
+                raise torch.linalg.LinAlgError(
+                    f"{where}: {what} ({e}); {undone}nothing was added to the {self.preserved} preserved rows") from e
+
     def apply(self, requests: List[Dict], cache_name: Optional[str] = None, return_orig_text_encoder: bool = False, shard=None,
               stage1=None):
         """One step: edit ``requests`` with every earlier step's keys preserved.  Returns what apply_emcid_to_text_encoder does."""
@@ -930,45 +984,13 @@ class EditSession:
         weights = self._weights()
         if self._orig is None:
             self._orig = {l: w.detach().clone() for l, w in weights.items()}
-        if self.keys is None:
-            w = next(iter(weights.values()))
-            if not w.is_cuda:
-                raise hip.EmcidHipError(f"the text encoder must live in HBM (got {w.device}); there is no CPU path")
-            self.keys = hip.PreservedKeys(len(self._fixed[2]), self.d, self.capacity, w.device)
+        self._ensure_keys()
         _announce(requests, self.verbose)
+        plan = self._run_plan(
+            lambda: prepare_text_encoder_edit(te, self.pipe.tokenizer, requests, hp, hp.layers, hp.mom2_update_weight, self.stats_dir,
+                                              cache_name, "", self.verbose, shard, _default_stage1(self.pipe, hp, stage1)),
+            True, "apply", "step", "new", f"session step {self.steps}", "the edited weights have been restored and ")
         LP = clip_forward.LAST_PATHS
-        for attempt in (0, 1):
-            plan = prepare_text_encoder_edit(te, self.pipe.tokenizer, requests, hp, hp.layers, hp.mom2_update_weight, self.stats_dir,
-                                             cache_name, "", self.verbose, shard, _default_stage1(self.pipe, hp, stage1))
-            plan.session = self
-            stats_flag = None
-            self._report_pending = None
-            try:
-                try:
-                    with phase("run + final sync"):
-                        run_encoder_edit(plan, keep_factors=False, restore=False)
-                except BaseException:
-                    plan.restore_weights()
-                    edit_engine._release_workspaces(plan)
-                    raise
-                # (check_info drops a failed plan's own factors: keep their flag word to tell which factorization said no)
-                stats_flag = plan.cov_factors.info if plan.cov_factors is not None else None
-                check_info(plan)                    # restores the weights itself before it raises
-            except clip_forward.StaleWeightCacheError as e:
-                # a weight was rewritten behind the forward's caches: the step is redone once from the live weights, M unchanged
-                if attempt == 1:
-                    raise
-                logging.getLogger("emcid_amd").warning("EditSession.apply: %s; redoing the step from the live weights", e)
-                clip_forward.invalidate_weight_caches(None)
-                LP["stale_cache_retries"] = LP.get("stale_cache_retries", 0) + 1
-                continue
-            except FloatingPointError as e:
-                what = "the statistics lam C' themselves are not positive definite" if stats_flag is not None and int(stats_flag.item()) \
-                    else f"the system of the new keys given the {self.preserved} preserved ones is not positive definite"
-                raise torch.linalg.LinAlgError(
-                    f"session step {self.steps}: {what} ({e}); the edited weights have been restored and nothing was added to "
-                    f"the {self.preserved} preserved rows") from e
-            break
         # all edited layers together: their rows are already behind row M
         self.keys.commit(n, hip.row_scale_of(self._fixed[1], plan.cov_factors, self._fixed[0]))
         self.steps += 1
@@ -1017,39 +1039,16 @@ class EditSession:
         if self.preserved + n > self.capacity:
             self.fold()
         hp, te = self.hparams, self.pipe.text_encoder
-        if self.keys is None:
-            wt = next(iter(self._weights().values()))
-            if not wt.is_cuda:
-                raise hip.EmcidHipError(f"the text encoder must live in HBM (got {wt.device}); there is no CPU path")
-            self.keys = hip.PreservedKeys(len(self._fixed[2]), self.d, self.capacity, wt.device)
-        LP = clip_forward.LAST_PATHS
-        for attempt in (0, 1):
+        self._ensure_keys()
+
+        def make_plan():
             plan = prepare_text_encoder_edit(te, self.pipe.tokenizer, requests, hp, hp.layers, hp.mom2_update_weight, self.stats_dir,
                                              None, "", self.verbose, shard, None, with_targets=False)
-            plan.session, plan.retain_weight = self, w
-            stats_flag = None
-            try:
-                try:
-                    with phase("run + final sync"):
-                        run_encoder_edit(plan, keep_factors=False, restore=False)       # (writes no weight)
-                except BaseException:
-                    edit_engine._release_workspaces(plan)
-                    raise
-                stats_flag = plan.cov_factors.info if plan.cov_factors is not None else None
-                check_info(plan)
-            except clip_forward.StaleWeightCacheError as e:
-                if attempt == 1:
-                    raise
-                logging.getLogger("emcid_amd").warning("EditSession.retain: %s; redoing the call from the live weights", e)
-                clip_forward.invalidate_weight_caches(None)
-                LP["stale_cache_retries"] = LP.get("stale_cache_retries", 0) + 1
-                continue
-            except FloatingPointError as e:
-                what = "the statistics lam C' themselves are not positive definite" if stats_flag is not None and int(stats_flag.item()) \
-                    else f"the system of the retained keys given the {self.preserved} preserved ones is not positive definite"
-                raise torch.linalg.LinAlgError(
-                    f"retain after step {self.steps}: {what} ({e}); nothing was added to the {self.preserved} preserved rows") from e
-            break
+            plan.retain_weight = w
+            return plan
+
+        plan = self._run_plan(make_plan, False, "retain", "call", "retained", f"retain after step {self.steps}")   # (writes no weight)
+        LP = clip_forward.LAST_PATHS
         self.keys.commit(n, hip.row_scale_of(self._fixed[1], plan.cov_factors, self._fixed[0], w))
         self.retained += n
         self._ledger += [(r.get("source"), "retain", self._retains, t) for r in requests for t in range(self._fixed[3])]
@@ -1109,10 +1108,7 @@ class EditSession:
         ws.info.zero_()
         for i in range(keys.n_layers):
             hip.session_release(keys, i, keep_dev, first, ws=ws)
-        flag = torch.empty(1, dtype=torch.int32, pin_memory=True)
-        flag.copy_(ws.info, non_blocking=True)
-        torch.cuda.current_stream(dev).synchronize()
-        code = int(flag.item())
+        code = self._read_flag(ws.info)
         if code != 0:
             for i, (y, l, t) in enumerate(snap):
                 keys.Yp[i][first:M].copy_(y)
@@ -1187,8 +1183,7 @@ def sweep_emcid_text_encoder(pipe, requests: List[Dict], hparams: EMCIDHyperPara
             import torch.distributed as dist
             if attempt or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
                 raise
-            logging.getLogger("emcid_amd").warning("sweep_emcid_text_encoder: %s; redoing the sweep from the live weights", e)
-            clip_forward.invalidate_weight_caches(None)
+            _note_stale("sweep_emcid_text_encoder", e, "sweep")
     # the hooked-HF forward has no stored state to replay: one ordinary call per point, restored after each
     clip_forward.note_fallback("sweep_emcid_text_encoder", clip_forward.UnsupportedEncoder("no prefix-trie forward: one call per point"))
     results = []

@@ -1278,21 +1278,58 @@ class PreservedKeys:
     def reset(self):
         self.M = 0
 
+    def check_layer(self, layer_index: int):
+        if not 0 <= layer_index < self.n_layers:
+            raise EmcidHipError(f"layer index {layer_index} outside the session state's {self.n_layers} layers")
+
+    def layer_args(self, layer_index: int):
+        """Layer ``layer_index``'s part of the state as the session entries of the library take it: (Yp, ldy, Lp, ldl, tile_inv,
+        capacity, M), the tensors as checked pointers into HBM.  Raises for a layer outside the state."""
+        self.check_layer(layer_index)
+        Yp, Lp, Ti = self.Yp[layer_index], self.Lp[layer_index], self.tile_inv[layer_index]
+        for t, nm in ((Yp, "Yp"), (Lp, "Lp"), (Ti, "tile_inv")):
+            assert t.stride(-1) == 1 and (t.dim() < 3 or t.is_contiguous()), nm
+        return (_ptr(Yp, torch.float64, "Yp"), Yp.stride(0), _ptr(Lp, torch.float64, "Lp"), Lp.stride(0),
+                _ptr(Ti, torch.float64, "tile_inv"), self.capacity, self.M)
+
     @property
     def nbytes(self) -> int:
         return sum(t.numel() * 8 for ts in (self.Yp, self.Lp, self.tile_inv) for t in ts)
 
 
-class PreserveWorkspace:
-    """HBM workspace (+ the device `info` word) of emcid_edit_layer_dual_preserve_f64 for steps of N rows at a given capacity."""
+class _SessionWorkspace:
+    """HBM workspace (+ the device `info` word) of one session entry of the library: ``size_fn(*dims.values())`` bytes, ``key``
+    the dimensions it was sized for."""
 
-    def __init__(self, N: int, d: int, h: int, capacity: int, device):
-        self.key = (N, d, h, capacity)
-        self.nbytes = int(load().emcid_edit_dual_preserve_workspace_bytes(N, d, h, capacity))
+    def __init__(self, what: str, size_fn, dims: dict, device):
+        self.key = tuple(dims.values())
+        self.nbytes = int(size_fn(*self.key))
         if self.nbytes <= 0:
-            raise EmcidHipError(f"no preserve workspace for N={N}, d={d}, h={h}, capacity={capacity}")
+            raise EmcidHipError(f"no {what} workspace for " + ", ".join(f"{k}={v}" for k, v in dims.items()))
         self.buf = torch.zeros(self.nbytes // 8, dtype=torch.float64, device=device)     # zero: the stream-K ticket counters
         self.info = torch.zeros(1, dtype=torch.int32, device=device)
+
+
+class PreserveWorkspace(_SessionWorkspace):
+    """The workspace of emcid_edit_layer_dual_preserve_f64 for steps of N rows at a given capacity."""
+
+    def __init__(self, N: int, d: int, h: int, capacity: int, device):
+        super().__init__("preserve", load().emcid_edit_dual_preserve_workspace_bytes, dict(N=N, d=d, h=h, capacity=capacity), device)
+
+
+class RetainWorkspace(_SessionWorkspace):
+    """The workspace of emcid_session_retain_f64 for retain calls of N rows at a given capacity."""
+
+    def __init__(self, N: int, d: int, capacity: int, device):
+        super().__init__("retain", load().emcid_session_retain_workspace_bytes, dict(N=N, d=d, capacity=capacity), device)
+
+
+class ReleaseWorkspace(_SessionWorkspace):
+    """The workspace of emcid_session_release_f64 for a release that rebuilds ``n_rebuilt`` rows: the retain workspace of that N."""
+
+    def __init__(self, n_rebuilt: int, d: int, capacity: int, device):
+        super().__init__("release", load().emcid_session_release_workspace_bytes, dict(n_rebuilt=n_rebuilt, d=d, capacity=capacity),
+                         device)
 
 
 def edit_layer_dual_preserve(K, Zc, zs_t, factors: CovFactors, layer_index: int, edit_weight: float, layers_left: int,
@@ -1307,8 +1344,7 @@ def edit_layer_dual_preserve(K, Zc, zs_t, factors: CovFactors, layer_index: int,
     for t, nm in ((K, "K"), (Zc, "Zc"), (zs_t, "zs_t")) + (((W, "W"), (W0, "W0")) if W is not None else ()):
         assert t.is_contiguous(), nm
     assert zs_t.shape == (N, h) and factors.d == d == state.d and (W is None or W.shape == (h, d))
-    if not 0 <= layer_index < state.n_layers:
-        raise EmcidHipError(f"layer index {layer_index} outside the session state's {state.n_layers} layers")
+    state.check_layer(layer_index)
     if layer_index not in factors.have_inverse:
         raise EmcidHipError("edit_layer_dual_preserve needs the explicit inverse factor of the layer (cov_inverse)")
     if state.M + N > state.capacity:
@@ -1317,26 +1353,12 @@ def edit_layer_dual_preserve(K, Zc, zs_t, factors: CovFactors, layer_index: int,
         ws = PreserveWorkspace(N, d, h, state.capacity, K.device)
     dW = torch.empty(h, d, dtype=torch.float32, device=K.device) if want_dw else None
     U = torch.empty(h, d, dtype=torch.float64, device=K.device) if want_u else None
-    Yp, Lp, Ti = state.Yp[layer_index], state.Lp[layer_index], state.tile_inv[layer_index]
     _check(load().emcid_edit_layer_dual_preserve_f64(
         _ptr(K, torch.float32, "K"), _ptr(Zc, torch.float32, "Zc"), _ptr(zs_t, torch.float32, "zs_t"), N, d, h,
         float(edit_weight), int(layers_left), factors.lam_ratio(lam), _ptr(factors.buf), factors.n_layers, int(layer_index),
-        _ptr(Yp, torch.float64, "Yp"), Yp.stride(0), _ptr(Lp, torch.float64, "Lp"), Lp.stride(0), _ptr(Ti, torch.float64, "tile_inv"),
-        state.capacity, state.M, _ptr(W0, torch.float32, "W0"), _ptr(W, torch.float32, "W"), _ptr(dW), _ptr(U),
+        *state.layer_args(layer_index), _ptr(W0, torch.float32, "W0"), _ptr(W, torch.float32, "W"), _ptr(dW), _ptr(U),
         _ptr(ws.buf), ws.nbytes, _ptr(ws.info, torch.int32), _stream(K)), "emcid_edit_layer_dual_preserve_f64")
     return {"dW": dW, "U": U, "ws": ws}
-
-
-class RetainWorkspace:
-    """HBM workspace (+ the device `info` word) of emcid_session_retain_f64 for retain calls of N rows at a given capacity."""
-
-    def __init__(self, N: int, d: int, capacity: int, device):
-        self.key = (N, d, capacity)
-        self.nbytes = int(load().emcid_session_retain_workspace_bytes(N, d, capacity))
-        if self.nbytes <= 0:
-            raise EmcidHipError(f"no retain workspace for N={N}, d={d}, capacity={capacity}")
-        self.buf = torch.zeros(self.nbytes // 8, dtype=torch.float64, device=device)     # zero: the stream-K ticket counters
-        self.info = torch.zeros(1, dtype=torch.int32, device=device)
 
 
 def row_scale_of(edit_weight: float, factors: CovFactors, lam: Optional[float] = None, weight: float = 1.0) -> float:
@@ -1354,8 +1376,7 @@ def session_retain(K, factors: CovFactors, layer_index: int, row_scale: float, s
     N, d = K.shape
     assert K.is_contiguous(), "K"
     assert factors.d == d == state.d
-    if not 0 <= layer_index < state.n_layers:
-        raise EmcidHipError(f"layer index {layer_index} outside the session state's {state.n_layers} layers")
+    state.check_layer(layer_index)
     if layer_index not in factors.have_inverse:
         raise EmcidHipError("session_retain needs the explicit inverse factor of the layer (cov_inverse)")
     if state.M + N > state.capacity:
@@ -1365,27 +1386,10 @@ def session_retain(K, factors: CovFactors, layer_index: int, row_scale: float, s
         raise EmcidHipError(f"row_scale must be positive and finite (got {row_scale})")
     if ws is None or ws.key != (N, d, state.capacity):
         ws = RetainWorkspace(N, d, state.capacity, K.device)
-    Yp, Lp, Ti = state.Yp[layer_index], state.Lp[layer_index], state.tile_inv[layer_index]
-    for t, nm in ((Yp, "Yp"), (Lp, "Lp"), (Ti, "tile_inv")):
-        assert t.stride(-1) == 1 and (t.dim() < 3 or t.is_contiguous()), nm
     _check(load().emcid_session_retain_f64(
         _ptr(K, torch.float32, "K"), N, d, row_scale, factors.lam_ratio(lam), _ptr(factors.buf), factors.n_layers, int(layer_index),
-        _ptr(Yp, torch.float64, "Yp"), Yp.stride(0), _ptr(Lp, torch.float64, "Lp"), Lp.stride(0), _ptr(Ti, torch.float64, "tile_inv"),
-        state.capacity, state.M, _ptr(ws.buf), ws.nbytes, _ptr(ws.info, torch.int32), _stream(K)), "emcid_session_retain_f64")
+        *state.layer_args(layer_index), _ptr(ws.buf), ws.nbytes, _ptr(ws.info, torch.int32), _stream(K)), "emcid_session_retain_f64")
     return {"ws": ws}
-
-
-class ReleaseWorkspace:
-    """HBM workspace (+ the device `info` word) of emcid_session_release_f64 for a release that rebuilds ``n_rebuilt`` rows: the
-    retain workspace of that N."""
-
-    def __init__(self, n_rebuilt: int, d: int, capacity: int, device):
-        self.key = (n_rebuilt, d, capacity)
-        self.nbytes = int(load().emcid_session_release_workspace_bytes(n_rebuilt, d, capacity))
-        if self.nbytes <= 0:
-            raise EmcidHipError(f"no release workspace for n_rebuilt={n_rebuilt}, d={d}, capacity={capacity}")
-        self.buf = torch.zeros(self.nbytes // 8, dtype=torch.float64, device=device)     # zero: the stream-K ticket counters
-        self.info = torch.zeros(1, dtype=torch.int32, device=device)
 
 
 def check_keep(keep, M: int):
@@ -1405,9 +1409,8 @@ def session_release(state: PreservedKeys, layer_index: int, keep, first: Optiona
     committed here (``state.release_commit(keep)`` after the flag word ``ws.info`` read zero, for all layers together).  A release
     of trailing rows only, or of every row, launches nothing.  ``keep`` may be an int32 tensor on the state's device holding the
     same indices (then ``first`` must be given and nothing is checked on the host).  Returns dict(ws | None, launched, first)."""
-    if not 0 <= layer_index < state.n_layers:
-        raise EmcidHipError(f"layer index {layer_index} outside the session state's {state.n_layers} layers")
-    Yp, Lp, Ti = state.Yp[layer_index], state.Lp[layer_index], state.tile_inv[layer_index]
+    state.check_layer(layer_index)
+    Yp = state.Yp[layer_index]
     if isinstance(keep, torch.Tensor) and keep.is_cuda:
         if first is None:
             raise EmcidHipError("session_release: a device tensor of kept rows needs `first`")
@@ -1428,11 +1431,8 @@ def session_release(state: PreservedKeys, layer_index: int, keep, first: Optiona
     n_rebuilt = n_keep - first
     if ws is None or ws.key != (n_rebuilt, state.d, state.capacity):
         ws = ReleaseWorkspace(n_rebuilt, state.d, state.capacity, Yp.device)
-    for t, nm in ((Yp, "Yp"), (Lp, "Lp"), (Ti, "tile_inv")):
-        assert t.stride(-1) == 1 and (t.dim() < 3 or t.is_contiguous()), nm
     _check(load().emcid_session_release_f64(
-        _ptr(keep_dev, torch.int32, "keep"), n_keep, first, state.d, _ptr(Yp, torch.float64, "Yp"), Yp.stride(0),
-        _ptr(Lp, torch.float64, "Lp"), Lp.stride(0), _ptr(Ti, torch.float64, "tile_inv"), state.capacity, state.M,
+        _ptr(keep_dev, torch.int32, "keep"), n_keep, first, state.d, *state.layer_args(layer_index),
         _ptr(ws.buf), ws.nbytes, _ptr(ws.info, torch.int32), _stream(Yp)), "emcid_session_release_f64")
     return {"ws": ws, "launched": True, "first": first}
 
@@ -1490,11 +1490,11 @@ def cov_factor_fold(src: CovFactors, state: PreservedKeys, layer_index: int, cov
         ws = torch.empty(need // 8, dtype=torch.float64, device=src.buf.device)
     if src.ready is not None:
         torch.cuda.current_stream(src.buf.device).wait_event(src.ready)
-    in_range = 0 <= layer_index < state.n_layers
-    Yp = state.Yp[layer_index if in_range else 0]
+    in_range = 0 <= layer_index < state.n_layers        # (a layer outside the state: the library refuses the call)
+    Yp, ldy = state.layer_args(layer_index if in_range else 0)[:2]
     base_l = base.view(src.n_layers, dp, dp)[layer_index if in_range else 0]
     _check(lib.emcid_cov_factor_fold_f64(
-        _ptr(src.buf), src.lam_ratio(lam), _ptr(Yp, torch.float64, "Yp"), Yp.stride(0), M, state.capacity,
+        _ptr(src.buf), src.lam_ratio(lam), Yp, ldy, M, state.capacity,
         _ptr(cov, torch.float32, "C"), float(lam), float(edit_weight), int(cov is not None), _ptr(dst.buf), src.n_layers, src.d,
         int(layer_index), _ptr(base_l, torch.float64, "base"), _ptr(ws, torch.float64, "ws"), ws.numel() * 8,
         _ptr(dst.info, torch.int32), _stream(src.buf)), "emcid_cov_factor_fold_f64")

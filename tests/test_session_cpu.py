@@ -4,17 +4,7 @@ import pytest
 import emcid_amd
 from emcid_amd import edit_engine as ee, emcid_main as em, hip, synthetic as syn
 from emcid_amd.emcid_hparams import EMCIDHyperParams, EMCIDXLHyperParams
-
-
-def _hp(**kw):
-    d = syn.sd_hparams_dict(layers=(1, 2, 3, 4), mom2_update_weight=50, edit_weight=0.6, mom2_n_samples=1000)
-    d.update(kw)
-    return EMCIDHyperParams(**d)
-
-
-@pytest.fixture(scope="module")
-def pipe():
-    return syn.build_pipe("toy", "cpu")
+from session_helpers import _hp, pipe  # noqa: F401  (pipe: a module-scoped fixture)
 
 
 def test_package_exports_the_session():

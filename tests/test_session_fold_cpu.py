@@ -9,19 +9,9 @@ import pytest
 import emcid_amd
 from emcid_amd import hip, synthetic as syn
 from emcid_amd.emcid_hparams import EMCIDHyperParams
+from session_helpers import _hp, pipe  # noqa: F401  (pipe: a module-scoped fixture)
 
 ROOT = Path(__file__).resolve().parents[1]
-
-
-def _hp(**kw):
-    d = syn.sd_hparams_dict(layers=(1, 2, 3, 4), mom2_update_weight=50, edit_weight=0.6, mom2_n_samples=1000)
-    d.update(kw)
-    return EMCIDHyperParams(**d)
-
-
-@pytest.fixture(scope="module")
-def pipe():
-    return syn.build_pipe("toy", "cpu")
 
 
 def test_abi_16_carries_the_fold_entry():

@@ -2,7 +2,6 @@
 recomputation of the primal system with ALL earlier keys in it, against a session that never folds, and against plain calls; what a
 fold leaves alone (the engine's factor cache, a refused fold's state) and what reset() / restore() drop.
 Run on the MI355X box:  python -m pytest tests/test_session_fold_gpu.py -m gpu -q"""
-import numpy as np
 import pytest
 import torch
 
@@ -12,75 +11,14 @@ import emcid_amd
 from emcid_amd import clip_forward as cf, edit_engine as ee, emcid_main as em, synthetic as syn
 from emcid_amd.emcid_hparams import EMCIDHyperParams
 from emcid_amd.nethook import get_parameter
-from oracle import emcid_oracle as orc
+import session_helpers as sh
+from session_helpers import BAR, DEV, _primal_step, _ratios, _weights
 
-DEV = "cuda:0"
-BAR = 1e-4          # the project's end-to-end bar: err <= 1e-4 max|dW| (tests/test_e2e_gpu.py, __graft_entry__.smoke)
-LAYERS = (1, 2, 3, 4)
-
-
-@pytest.fixture(autouse=True)
-def _fresh_caches():
-    em.clear_caches()
-    ee.clear_engine_caches()
-    yield
-    em.clear_caches()
-    ee.clear_engine_caches()
+_fresh_caches = sh.fresh_caches(engine=True)
 
 
 def _setup(tmp_path, n_req=13, k=1):
-    reqs = syn.make_requests(n_req, ragged=True)
-    hp_d = syn.sd_hparams_dict(layers=LAYERS, mom2_update_weight=50, edit_weight=0.6, mom2_n_samples=1000)
-    if k > 1:
-        hp_d.update(num_edit_tokens=k, use_new_compute_z=True)
-    names = [hp_d["rewrite_module_tmp"].format(l) for l in hp_d["layers"]]
-    cache, stats = str(tmp_path / "cache") + "/", str(tmp_path / "stats")
-    if k > 1:
-        rng = np.random.default_rng(1)
-        for r in reqs:
-            p = syn.vstar_cache_path(cache, r)
-            p.parent.mkdir(parents=True, exist_ok=True)
-            np.savez(p, v_star=(rng.standard_normal((k, 32)) * 0.5).astype(np.float32))
-    else:
-        syn.write_vstar_cache(cache, reqs, 32, seed=1, scale=0.5)
-    syn.write_stats_cache(stats, names, 128, 1000, seed=2, t=512)
-    return reqs, hp_d, names, cache, stats
-
-
-def _weights(te, names):
-    return {n: get_parameter(te, n + ".weight").detach().cpu().double() for n in names}
-
-
-def _primal_step(gpu_te, reqs, hp_d, names, cache, stats, P, k=1):
-    """One step recomputed in fp64 from the primal system, layer by layer, on a CPU copy of the encoder AS IT IS NOW;
-    A = lam C' + sum_{earlier steps} P^T P + Kt^T Kt with EVERY earlier step's keys, folded or not.  Appends this step's Kt to ``P``;
-    returns ({name: dW f64}, {name: K f64})."""
-    cpu = syn.build_pipe("toy", "cpu")
-    cpu.text_encoder.load_state_dict({n: v.detach().cpu() for n, v in gpu_te.state_dict().items()})
-    te, tok = cpu.text_encoder, cpu.tokenizer
-    lam, e, L = float(hp_d["mom2_update_weight"]), float(hp_d["edit_weight"]), len(names)
-    zs = orc.load_vstars(cache, reqs, use_new_compute_z=k > 1)          # (h, N k)
-    s = (e / 0.5) ** 0.5
-    dws, keys = {}, {}
-    with torch.no_grad():
-        for i, n in enumerate(names):
-            if k > 1:
-                K, Zc = orc.module_input_output_at_words_multi(te, tok, reqs, n, k)
-                K, Zc = K.reshape(-1, K.shape[-1]), Zc.reshape(-1, Zc.shape[-1])
-            else:
-                K, Zc = orc.module_input_output_at_words(te, tok, reqs, n)
-            C = orc.load_cov(stats, n, hp_d["mom2_n_samples"], hp_d["mom2_dtype"])
-            Cp = (C * (1 - e) / 0.5).double()
-            Kt, Rt = s * K.double(), (s * (zs.t() - Zc).double()) / (L - i)
-            A = lam * Cp + Kt.t() @ Kt
-            for Pk in P.setdefault(n, []):
-                A = A + Pk.t() @ Pk
-            upd = torch.linalg.solve(A, Kt.t() @ Rt).t()
-            w = orc.get_parameter(te, n + ".weight")
-            w[...] = w + upd.float()
-            P[n].append(Kt)
-            dws[n], keys[n] = upd, K.double()
-    return dws, keys
+    return sh._setup(tmp_path, n_req, k)
 
 
 def _run(fx, sizes, k=1, primal=False, fold_after=(), **session_kw):
@@ -93,7 +31,7 @@ def _run(fx, sizes, k=1, primal=False, fold_after=(), **session_kw):
     for t, n in enumerate(sizes):
         step = reqs[lo:lo + n]
         if primal:
-            r, kk = _primal_step(pipe.text_encoder, step, hp_d, names, cache, stats, P, k)
+            r, _, _, kk = _primal_step(pipe.text_encoder, step, hp_d, names, cache, stats, P, k)
             ref.append(r), keys.append(kk)
         before = _weights(pipe.text_encoder, names)
         sess.apply(step, cache_name=cache)
@@ -116,11 +54,6 @@ def _close(a, b, names, what):
         err, scale = (a[n] - b[n]).abs().max().item(), b[n].abs().max().item()
         print(f"{what} {n}: {err:.3e} of max|dW| {scale:.3e}")
         assert err <= BAR * scale, (what, n, err, scale)
-
-
-def _ratios(dw1, dw2, keys1, names):
-    """per layer and key of step 1: ||dW2 k|| / ||dW1 k||"""
-    return {n: (dw2[n] @ keys1[n].t()).norm(dim=0) / (dw1[n] @ keys1[n].t()).norm(dim=0) for n in names}
 
 
 def test_on_full_fold_keeps_the_folded_keys_preserved(tmp_path, monkeypatch):

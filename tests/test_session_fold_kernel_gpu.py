@@ -3,7 +3,7 @@ after a fold the workspace holds the factor of lam C' + P^T P (P: the keys of th
 inverse, and a step on it with an empty state solves the system a never-folding session solves.  The references are formed here, on
 the CPU in fp64: numpy's Cholesky of the primal matrix and torch.linalg.solve on it.
 
-Same input recipe as tests/test_session_kernel_gpu.py (d = 384, h = 96, lam = 50, edit_weight 0.6, nearly collinear rows, Cov with a
+The input recipe of tests/session_kernel_helpers.py (d = 384, h = 96, lam = 50, edit_weight 0.6, nearly collinear rows, Cov with a
 1 600 condition number).  The same algebra on the CPU in fp64 gives L' within 6e-16 .. 7e-16 and U within 3e-15 .. 2e-13 of these
 references, six to seven orders inside the bars; the values the MI355X gives are in DESIGN.md §3."""
 import ctypes as C
@@ -16,45 +16,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from emcid_amd import hip
-
-DEV = "cuda:0"
-D, H, LAM, EW, LEFT = 384, 96, 50.0, 0.6, 2
-# the bars of the existing fp64 tests (tests/test_kernels_gpu.py, tests/test_session_kernel_gpu.py): 1e-8 of max|U| for a solve
-# result, 1e-9 of the largest entry for a Cholesky factor
-U_BAR, L_BAR = 1e-8, 1e-9
-
-
-@functools.lru_cache(maxsize=None)
-def _inputs(total, d=D):
-    """`total` key rows (a few of them nearly collinear), targets and statistics; computed once per size, never written."""
-    g = torch.Generator().manual_seed(1000 + total)
-    K = torch.randn(total, d, generator=g) * 0.3
-    K[1] = K[0] + 1e-4 * torch.randn(d, generator=g)
-    K[total - 1] = K[0] * 0.5 + K[2] * 0.5 + 1e-4 * torch.randn(d, generator=g)
-    if total > 140:
-        K[135] = K[3] + 1e-4 * torch.randn(d, generator=g)
-    Zc = torch.randn(total, H, generator=g)
-    zs_t = torch.randn(total, H, generator=g)
-    x = torch.randn(2 * d, d, generator=g) * torch.exp(torch.linspace(0, -3, d))
-    Cov = (x.t() @ x) / (2 * d)
-    W0 = torch.randn(H, d, generator=g) * 0.02
-    return K, Zc, zs_t, Cov, W0
-
-
-def _scaled(K, Zc, zs_t):
-    s = (EW / 0.5) ** 0.5
-    return s * K.double(), (s * (zs_t - Zc).double()) / LEFT
-
-
-def _primal_matrix(K, Zc, zs_t, Cov, hi):
-    Kt, _ = _scaled(K, Zc, zs_t)
-    return LAM * ((Cov * (1 - EW)) / 0.5).double() + Kt[:hi].t() @ Kt[:hi]
-
-
-def _primal_u(K, Zc, zs_t, Cov, lo, hi):
-    """U = Rt^T Kt (lam C' + P^T P + Kt^T Kt)^-1 for the step of rows [lo, hi) with rows [0, lo) in the system."""
-    Kt, Rt = _scaled(K, Zc, zs_t)
-    return torch.linalg.solve(_primal_matrix(K, Zc, zs_t, Cov, hi), Kt[lo:hi].t() @ Rt[lo:hi]).t()
+from session_kernel_helpers import D, DEV, EW, H, LAM, LEFT, L_BAR, U_BAR, _inputs, _primal_matrix, _primal_u
 
 
 def _step(inp, lo, n, fac, state):

@@ -1,7 +1,6 @@
 """EditSession end to end on the toy encoder with cached v* files: a step against apply_emcid_to_text_encoder, several steps
 against an fp64 recomputation of the primal system lam C' + sum P^T P + Kt^T Kt on the CPU, what a session preserves that plain
 calls do not, and its bookkeeping.  Run on the MI355X box:  python -m pytest tests/test_session_gpu.py -m gpu -q"""
-import numpy as np
 import pytest
 import torch
 
@@ -11,73 +10,9 @@ import emcid_amd
 from emcid_amd import clip_forward as cf, edit_engine as ee, emcid_main as em, synthetic as syn
 from emcid_amd.emcid_hparams import EMCIDHyperParams
 from emcid_amd.nethook import get_parameter
-from oracle import emcid_oracle as orc
+from session_helpers import BAR, DEV, _primal_step, _ratios, _setup, _weights, fresh_caches
 
-DEV = "cuda:0"
-BAR = 1e-4          # the project's end-to-end bar: err <= 1e-4 max|dW| (tests/test_e2e_gpu.py, __graft_entry__.smoke)
-LAYERS = (1, 2, 3, 4)
-
-
-@pytest.fixture(autouse=True)
-def _fresh_caches():
-    em.clear_caches()
-    yield
-    em.clear_caches()
-
-
-def _setup(tmp_path, n_req=12, k=1):
-    reqs = syn.make_requests(n_req, ragged=True)
-    hp_d = syn.sd_hparams_dict(layers=LAYERS, mom2_update_weight=50, edit_weight=0.6, mom2_n_samples=1000)
-    if k > 1:
-        hp_d.update(num_edit_tokens=k, use_new_compute_z=True)
-    names = [hp_d["rewrite_module_tmp"].format(l) for l in hp_d["layers"]]
-    cache, stats = str(tmp_path / "cache") + "/", str(tmp_path / "stats")
-    if k > 1:
-        rng = np.random.default_rng(1)
-        for r in reqs:
-            p = syn.vstar_cache_path(cache, r)
-            p.parent.mkdir(parents=True, exist_ok=True)
-            np.savez(p, v_star=(rng.standard_normal((k, 32)) * 0.5).astype(np.float32))
-    else:
-        syn.write_vstar_cache(cache, reqs, 32, seed=1, scale=0.5)
-    syn.write_stats_cache(stats, names, 128, 1000, seed=2, t=512)
-    return reqs, hp_d, names, cache, stats
-
-
-def _weights(te, names):
-    return {n: get_parameter(te, n + ".weight").detach().cpu().double() for n in names}
-
-
-def _primal_step(gpu_te, reqs, hp_d, names, cache, stats, P, k=1):
-    """One step recomputed in fp64 from the primal system, layer by layer, on a CPU copy of the encoder AS IT IS NOW: the keys of
-    every edited layer come from a hooked forward on the current weights (the earlier layers of this step already updated);
-    A = lam C' + sum_{earlier steps} P^T P + Kt^T Kt.  Appends this step's Kt to ``P``; returns ({name: dW f64}, {name: K fp32})."""
-    cpu = syn.build_pipe("toy", "cpu")
-    cpu.text_encoder.load_state_dict({n: v.detach().cpu() for n, v in gpu_te.state_dict().items()})
-    te, tok = cpu.text_encoder, cpu.tokenizer
-    lam, e, L = float(hp_d["mom2_update_weight"]), float(hp_d["edit_weight"]), len(names)
-    zs = orc.load_vstars(cache, reqs, use_new_compute_z=k > 1)          # (h, N k)
-    s = (e / 0.5) ** 0.5
-    dws, keys = {}, {}
-    with torch.no_grad():
-        for i, n in enumerate(names):
-            if k > 1:
-                K, Zc = orc.module_input_output_at_words_multi(te, tok, reqs, n, k)
-                K, Zc = K.reshape(-1, K.shape[-1]), Zc.reshape(-1, Zc.shape[-1])
-            else:
-                K, Zc = orc.module_input_output_at_words(te, tok, reqs, n)
-            C = orc.load_cov(stats, n, hp_d["mom2_n_samples"], hp_d["mom2_dtype"])
-            Cp = (C * (1 - e) / 0.5).double()
-            Kt, Rt = s * K.double(), (s * (zs.t() - Zc).double()) / (L - i)
-            A = lam * Cp + Kt.t() @ Kt
-            for Pk in P.setdefault(n, []):
-                A = A + Pk.t() @ Pk
-            upd = torch.linalg.solve(A, Kt.t() @ Rt).t()
-            w = orc.get_parameter(te, n + ".weight")
-            w[...] = w + upd.float()
-            P[n].append(Kt)
-            dws[n], keys[n] = upd, K.double()
-    return dws, keys
+_fresh_caches = fresh_caches()
 
 
 def _session_steps(tmp_path, sizes, k=1, capacity=None):
@@ -90,7 +25,7 @@ def _session_steps(tmp_path, sizes, k=1, capacity=None):
     P, got, ref, keys, lo = {}, [], [], [], 0
     for t, n in enumerate(sizes):
         step = reqs[lo:lo + n]
-        r, kk = _primal_step(pipe.text_encoder, step, hp_d, names, cache, stats, P, k)
+        r, _, _, kk = _primal_step(pipe.text_encoder, step, hp_d, names, cache, stats, P, k)
         before = _weights(pipe.text_encoder, names)
         out = sess.apply(step, cache_name=cache)
         assert out[0] is pipe and out[1] is None
@@ -134,11 +69,6 @@ def test_multi_token_session_matches_primal(tmp_path):
     """(e) num_edit_tokens = 2: rows are concepts (N k per step), one two-step session against the primal recomputation."""
     _, _, _, sess, _, _ = _session_steps(tmp_path, (4, 3), k=2)
     assert sess.preserved == 14
-
-
-def _ratios(dw1, dw2, keys1, names):
-    """per layer and key of step 1: ||dW2 k|| / ||dW1 k||"""
-    return {n: (dw2[n] @ keys1[n].t()).norm(dim=0) / (dw1[n] @ keys1[n].t()).norm(dim=0) for n in names}
 
 
 def test_session_preserves_what_plain_calls_move(tmp_path):
@@ -222,7 +152,7 @@ def test_stale_cache_retry_leaves_the_preserved_count(tmp_path):
     v = w._version
     w.data.copy_(w.data * 1.25)
     assert w._version == v                      # invisible to the version counter
-    ref, _ = _primal_step(pipe.text_encoder, reqs[5:9], hp_d, names, cache, stats, P)
+    ref = _primal_step(pipe.text_encoder, reqs[5:9], hp_d, names, cache, stats, P)[0]
     retries = cf.LAST_PATHS.get("stale_cache_retries", 0)
     before = _weights(pipe.text_encoder, names)
     sess.apply(reqs[5:9], cache_name=cache)

@@ -1,8 +1,6 @@
 """The dual solver with a preserved key set (emcid_edit_layer_dual_preserve_f64, include/emcid_hip.h) through the C ABI, no encoder:
 a later step must solve against A = lam C' + P^T P + Kt^T Kt, P the stacked keys of the earlier steps, and append [Lkp Lkk] to the
 state's Cholesky factor.  The reference is formed here, on the CPU in fp64, from the primal system."""
-import functools
-
 import numpy as np
 import pytest
 import torch
@@ -10,43 +8,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from emcid_amd import hip
-
-DEV = "cuda:0"
-D, H, LAM, EW, LEFT = 384, 96, 50.0, 0.6, 2
-# the bars of the existing fp64 solve-vs-oracle tests (tests/test_kernels_gpu.py): 1e-8 of the largest entry for an fp64 solve
-# result (adj_k there, U here), 1e-9 for a Cholesky factor
-U_BAR, L_BAR = 1e-8, 1e-9
-
-
-@functools.lru_cache(maxsize=None)
-def _inputs(total):
-    """`total` key rows (a few of them nearly collinear: inside the first step, and a later row with a row of the first step),
-    targets, statistics and their factors; computed once per size and shared, never written."""
-    g = torch.Generator().manual_seed(1000 + total)
-    K = torch.randn(total, D, generator=g) * 0.3
-    K[1] = K[0] + 1e-4 * torch.randn(D, generator=g)
-    K[total - 1] = K[0] * 0.5 + K[2] * 0.5 + 1e-4 * torch.randn(D, generator=g)
-    if total > 140:
-        K[135] = K[3] + 1e-4 * torch.randn(D, generator=g)
-    Zc = torch.randn(total, H, generator=g)
-    zs_t = torch.randn(total, H, generator=g)
-    x = torch.randn(2 * D, D, generator=g) * torch.exp(torch.linspace(0, -3, D))
-    Cov = (x.t() @ x) / (2 * D)
-    W0 = torch.randn(H, D, generator=g) * 0.02
-    return K, Zc, zs_t, Cov, W0
-
-
-def _scaled(K, Zc, zs_t):
-    s = (EW / 0.5) ** 0.5
-    return s * K.double(), (s * (zs_t - Zc).double()) / LEFT
-
-
-def _primal_u(K, Zc, zs_t, Cov, lo, hi):
-    """U = Rt^T Kt (lam C' + P^T P + Kt^T Kt)^-1 for the step of rows [lo, hi) with rows [0, lo) preserved."""
-    Kt, Rt = _scaled(K, Zc, zs_t)
-    Cp = ((Cov * (1 - EW)) / 0.5).double()
-    A = LAM * Cp + Kt[:hi].t() @ Kt[:hi]
-    return torch.linalg.solve(A, Kt[lo:hi].t() @ Rt[lo:hi]).t()
+from session_kernel_helpers import D, DEV, EW, H, LAM, LEFT, L_BAR, U_BAR, _inputs, _primal_u, _scaled
 
 
 def _dual_u(K, Zc, zs_t, Cov, lo, hi):

@@ -9,19 +9,9 @@ import torch
 import emcid_amd
 from emcid_amd import emcid_main as em, hip, synthetic as syn
 from emcid_amd.emcid_hparams import EMCIDHyperParams
+from session_helpers import _hp, pipe  # noqa: F401  (pipe: a module-scoped fixture)
 
 NEW = ("emcid_session_release_workspace_bytes", "emcid_session_release_f64")
-
-
-def _hp(**kw):
-    d = syn.sd_hparams_dict(layers=(1, 2, 3, 4), mom2_update_weight=50, edit_weight=0.6, mom2_n_samples=1000)
-    d.update(kw)
-    return EMCIDHyperParams(**d)
-
-
-@pytest.fixture(scope="module")
-def pipe():
-    return syn.build_pipe("toy", "cpu")
 
 
 def test_symbols_are_exported_and_bound():

@@ -1,23 +1,17 @@
 """EditSession.release end to end on the toy encoder: a released concept's rows leave the preserved set without a weight moving, the
 steps after it are those of the primal system lam C' + P^T P + Kt^T Kt with the released rows taken out of P (recomputed on the CPU in
 fp64), and a re-edit lands where a session that still holds the old rows cannot reach.  The fixture recipe, the helpers and the bar
-are those of tests/test_session_retain_gpu.py.
+are those of tests/session_helpers.py.
 Run on the MI355X box:  python -m pytest tests/test_session_release_gpu.py -m gpu -q"""
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
-import emcid_amd
-from emcid_amd import clip_forward as cf, emcid_main as em, hip, synthetic as syn
-from test_session_retain_gpu import BAR, _apply_checked, _held, _keys, _primal_step, _seed, _session, _setup, _weights
+from emcid_amd import clip_forward as cf, hip, synthetic as syn
+from session_helpers import _apply_checked, _held, _keys, _seed, _session, _setup, _weights, fresh_caches
 
-
-@pytest.fixture(autouse=True)
-def _fresh_caches():
-    em.clear_caches()
-    yield
-    em.clear_caches()
+_fresh_caches = fresh_caches()
 
 
 def _params(pipe):

@@ -1,7 +1,7 @@
 """emcid_session_release_f64 (include/emcid_hip.h) through the binding, no encoder: after a release the state must be the state of
 the kept rows alone — Yp' the kept rows bit for bit, Lp' = chol(I + Yp' Yp'^T), the tile inverses those of its diagonal tiles — with
 rows below the smallest released index never written, and a step on it must be the primal solve without the released keys.  The
-references are formed here, on the CPU in fp64.  Inputs, helpers and bars are those of tests/test_session_retain_kernel_gpu.py."""
+references are formed here, on the CPU in fp64.  Inputs, helpers and bars are those of tests/session_kernel_helpers.py."""
 import functools
 
 import numpy as np
@@ -11,7 +11,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from emcid_amd import hip
-from test_session_retain_kernel_gpu import DEV, EW, H, LAM, LEFT, L_BAR, U_BAR, _cp, _dev, _inputs, _retain, _scale, _step
+from session_kernel_helpers import DEV, EW, H, LAM, LEFT, L_BAR, U_BAR, _cp, _dev, _inputs_by_width as _inputs, _retain, _scale, _step
 
 NSTEP = 6                       # rows of the step that follows every release
 CHUNK = 70                      # the state is seeded by retain lists of at most this many rows

@@ -1,10 +1,7 @@
 """emcid_session_retain_f64 and emcid_session_step_norms_f64 (include/emcid_hip.h) through the binding, no encoder: a retain list
 must append exactly the rows a preserve step with a zero residual appends — Yk = Kt X^T, [Lkp Lkk] of chol(I + Y Y^T), the touched
 tile inverses — without touching rows below M, and the norms must be those of dW p_i = -Zp_i, Zk_j = Rt_j - dW Kt_j and Rt_j.
-The references are formed here, on the CPU in fp64.  Inputs and bars are those of tests/test_session_kernel_gpu.py."""
-import functools
-import math
-
+The references are formed here, on the CPU in fp64.  Inputs and bars are those of tests/session_kernel_helpers.py."""
 import numpy as np
 import pytest
 import torch
@@ -12,58 +9,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from emcid_amd import hip
+from session_kernel_helpers import DEV, EW, H, LAM, LEFT, L_BAR, U_BAR, _cp, _dev, _inputs_by_width as _inputs, _retain, _scale, _step
 
-DEV = "cuda:0"
-H, LAM, EW, LEFT = 96, 50.0, 0.6, 2
-U_BAR, L_BAR = 1e-8, 1e-9          # of the largest entry for an fp64 solve result (Yk, U); for a Cholesky factor
 SAME = 1e-13                       # two fp64 chains over the same launches, relative to the largest entry
 CASES = [(0, 5), (5, 3), (130, 70), (200, 129)]      # one tile; a tile boundary inside the append; a last partial tile
-
-
-@functools.lru_cache(maxsize=None)
-def _inputs(total, d=384):
-    """`total` key rows (a few nearly collinear: inside the first rows, and the last row with two of the first), targets and
-    statistics; computed once per size and shared, never written."""
-    g = torch.Generator().manual_seed(1000 + total + d)
-    K = torch.randn(total, d, generator=g) * 0.3
-    K[1] = K[0] + 1e-4 * torch.randn(d, generator=g)
-    K[total - 1] = K[0] * 0.5 + K[2] * 0.5 + 1e-4 * torch.randn(d, generator=g)
-    if total > 140:
-        K[135] = K[3] + 1e-4 * torch.randn(d, generator=g)
-    Zc = torch.randn(total, H, generator=g)
-    zs_t = torch.randn(total, H, generator=g)
-    x = torch.randn(2 * d, d, generator=g) * torch.exp(torch.linspace(0, -3, d))
-    Cov = (x.t() @ x) / (2 * d)
-    W0 = torch.randn(H, d, generator=g) * 0.02
-    return K, Zc, zs_t, Cov, W0
-
-
-def _dev(t):
-    return t.contiguous().to(DEV)
-
-
-def _cp(Cov):
-    return ((Cov * (1 - EW)) / 0.5).double()
-
-
-def _scale(weight=1.0):
-    return math.sqrt(weight * EW / 0.5)
-
-
-def _retain(K, fac, state, weight=1.0, commit=True):
-    res = hip.session_retain(_dev(K), fac, 0, _scale(weight), state)
-    flag = int(res["ws"].info.item())
-    if commit and flag == 0:
-        state.commit(K.shape[0], hip.row_scale_of(EW, fac, LAM, weight))
-    return flag
-
-
-def _step(K, Zc, zs_t, W0, fac, state):
-    W = torch.empty(H, K.shape[1], dtype=torch.float32, device=DEV)
-    res = hip.edit_layer_dual_preserve(_dev(K), _dev(Zc), _dev(zs_t), fac, 0, EW, LEFT, _dev(W0), W, state, want_u=True)
-    assert int(res["ws"].info.item()) == 0
-    res["W"] = W
-    return res
 
 
 def _y_ref(K, Cov, scale):
