@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <stdlib.h>
+#include <functional>
 #include <initializer_list>
 
 #include "../../include/emcid_hip.h"
@@ -32,7 +33,13 @@ inline int check_launch(const char* fn) {
         if (!(cond)) return ::emcid::fail(EMCID_ERR_BAD_ARG, __func__, "bad argument: " #cond); \
     } while (0)
 
-#define EMCID_CHECK_LAUNCH()                          \
+// the size check of every entry that takes (workspace, workspace_bytes); tail: "" or " (see <its size function>)"
+#define EMCID_CHECK_WORKSPACE(have_bytes, need_bytes, tail)                                                               \
+    do {                                                                                                                  \
+        if ((have_bytes) < (need_bytes)) return ::emcid::fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small" tail); \
+    } while (0)
+
+#define EMCID_CHECK_LAUNCH()                        \
     do {                                              \
         int rc_ = ::emcid::check_launch(__func__);    \
         if (rc_) return rc_;                          \
@@ -60,6 +67,25 @@ struct ScopedProf {
     ScopedProf(int c, hipStream_t s) : cls(c), st(s) { prof_begin(cls, st); }
     ~ScopedProf() { prof_end(cls, st); }
 };
+
+int env_flag(const char* name, int dflt);      // atoi of an environment variable, dflt when it is not set
+
+// ---- chains of launches as cached hipGraphs (runtime.hip: one cache, one mutex, one set of capture streams) -------------
+// A key is the workspace pointers and sizes that fully determine a chain of launches, and the tag of the chain: two chains
+// that could meet on the same pointers and sizes must not share a tag, or one would replay the other's graph.
+enum GraphTag : int {
+    GRAPH_FACTOR_SOLVE = 1, GRAPH_FACTOR_COV = 2, GRAPH_DUAL_STAGE1 = 3, GRAPH_DUAL_STAGE2 = 4, GRAPH_APPLY_STAGE1 = 5,
+    GRAPH_APPLY_STAGE2 = 6, GRAPH_COV_INVERSE = 7, GRAPH_COLS_STAGE2 = 8
+};
+struct GraphKey {
+    const void* ptr[8];
+    int64_t num[6];       // num[5]: the tag
+    int64_t dev;          // device the launches were captured for (filled in by with_graph)
+    bool operator==(const GraphKey& o) const { return memcmp(this, &o, sizeof(GraphKey)) == 0; }
+};
+GraphKey make_key(GraphTag tag, std::initializer_list<const void*> ptrs, std::initializer_list<int64_t> nums);
+// Runs `body(stream)` — a chain of launches whose arguments are fully determined by `key` — as a cached hipGraph.
+int with_graph(const GraphKey& key, hipStream_t st, const std::function<int(hipStream_t)>& body);
 
 constexpr int NB = 128;  // Cholesky block size (diagonal leaf)
 constexpr int OB = 512;  // outer block of the triangular solves: the inverse of each OB x OB diagonal block of L is formed

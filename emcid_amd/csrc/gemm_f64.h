@@ -949,8 +949,9 @@ inline void launch_gemm_f64_streamk2_bk(GemmShape p, EpiAxpby epi, hipStream_t s
 inline bool streamk2_fits(int64_t M, int64_t N) { return ((M + 127) / 128) * ((N + 127) / 128) <= 16384; }
 
 // Returns false (nothing launched) when the product has more tiles than ticket counters: the caller takes another form.
+// (not `inline`, like launch_gemm_f64 below: an `extern template` declaration then keeps a unit from instantiating the kernels)
 template <bool KCA, bool KCB>
-[[nodiscard]] inline bool launch_gemm_f64_streamk2(GemmShape p, EpiAxpby epi, hipStream_t stream, int wgs, double* work,
+[[nodiscard]] bool launch_gemm_f64_streamk2(GemmShape p, EpiAxpby epi, hipStream_t stream, int wgs, double* work,
                                                    double diag_add = 0.0) {
     if (!streamk2_fits(p.M, p.N)) return false;
     launch_gemm_f64_streamk2_bk<KCA, KCB, 16>(p, epi, stream, wgs, work, diag_add);
@@ -965,7 +966,7 @@ template <class Epi> inline void epi_set_atomic(Epi&) {}
 inline void epi_set_atomic(EpiAxpby& e) { e.atomic = 1; }
 
 template <bool KCA, bool KCB, class Epi>
-inline void launch_gemm_f64(GemmShape p, Epi epi, hipStream_t stream, int force_cfg = -1) {
+void launch_gemm_f64(GemmShape p, Epi epi, hipStream_t stream, int force_cfg = -1) {
     // cfg 0: 128x128 tile, 8 waves  — when that many tiles still fill the chip
     // cfg 1: 64x64 tile, 4 waves    — 4x the workgroups
     // cfg 2: 32x64 tile, 4 waves    — skinny problems (M ~ number of concepts); needs a K-contiguous A operand

@@ -257,7 +257,7 @@ int emcid_edit_layer_lu_f64(const float* K, const float* Zc, const float* zs_t, 
     EMCID_CHECK_ARG(N < (1 << 24) && d <= 32768 && h <= 32768 && aligned16(workspace));
     EMCID_CHECK_ARG((W == nullptr) || (W0 != nullptr));
     LuWorkspace ws(N, d, h);
-    if (workspace_bytes < ws.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
+    EMCID_CHECK_WORKSPACE(workspace_bytes, ws.total * (int64_t)sizeof(double), "");
     hipStream_t st = (hipStream_t)stream;
     double* base = (double*)workspace;
     double *A = base + ws.off_A, *Kt = base + ws.off_K, *R = base + ws.off_R, *X = base + ws.off_X;

@@ -1,163 +1,14 @@
-// Stage 2 of EMCID on gfx950: assemble A = lam*C' + K K^T, blocked fp64 Cholesky, blocked TRSM with the
-// N concept columns as right-hand sides, dW = R X^T and the in-place fp32 weight update.
-// Replaces emcid/emcid_main.py:1016-1061 of the reference (torch.linalg.solve + `@` in fp64).
+// The dense SPD algebra of stage 2 on gfx950: blocked fp64 Cholesky (device code and both host schedules), the inverses of
+// the diagonal blocks, the blocked triangular solves, the explicit inverse of a factor and the two products against it.
+// Replaces torch.linalg.solve in fp64 of the reference (emcid/emcid_main.py:1016-1061); the solvers that call this are in
+// edit_solve.hip and session.hip.
 //
 // Everything dense runs through gemm_f64.h (v_mfma_f64_16x16x4_f64).  The Cholesky is right-looking
 // with NB = 128: a single-workgroup LDS leaf factors the diagonal block and inverts it, so the panel
 // solve and every later triangular solve are MFMA GEMMs against the inverted diagonal blocks.
-#include <functional>
-#include <mutex>
-
-#include "common.h"
-#include "gemm_f64.h"
+#include "spd_solve.h"
 
 namespace emcid {
-
-thread_local char g_last_error[512] = "";
-
-// ---- profiling state ------------------------------------------------------------------------------------
-namespace {
-constexpr int PROF_MAX = 16384;
-unsigned g_prof_mask = 0;
-int g_prof_n = 0;
-hipEvent_t g_prof_ev[PROF_MAX][2];
-int g_prof_cls[PROF_MAX];
-bool g_prof_init = false;
-}  // namespace
-
-void prof_begin(int cls, hipStream_t st) {
-    if (!(g_prof_mask & (1u << cls)) || g_prof_n >= PROF_MAX) return;
-    g_prof_cls[g_prof_n] = cls;
-    (void)hipEventRecord(g_prof_ev[g_prof_n][0], st);
-}
-void prof_end(int cls, hipStream_t st) {
-    if (!(g_prof_mask & (1u << cls)) || g_prof_n >= PROF_MAX) return;
-    (void)hipEventRecord(g_prof_ev[g_prof_n][1], st);
-    ++g_prof_n;
-}
-
-// ---- element-wise preparation ---------------------------------------------------------------------
-
-// Kt64[n][j] = double(K[n][j]) * s * g (zero padded to [Np][dp]);
-// Rt[n][i]   = double(zs_t[n][i] - Zc[n][i]) * s / layers_left * g  (fp32 subtract first, like the reference).
-// g = 1 for the direct solver.  The dual solver passes g = sqrt(lam_factored / lam): it then works with a factor of
-// lam_factored * C' whatever the call's lam is (chol(lam C') = sqrt(lam) chol(C')), see emcid_factor_cov_f64.
-__global__ __launch_bounds__(256) void prep_kr_kernel(const float* __restrict__ K, const float* __restrict__ Zc,
-                                                       const float* __restrict__ zs_t, int N, int d, int h, double s,
-                                                       double layers_left, double* __restrict__ Kt64, int Np, int dp,
-                                                       double* __restrict__ Rt, int hp, double g = 1.0) {
-    const int n = blockIdx.x;
-    for (int j = threadIdx.x; j < dp; j += 256) {
-        double v = 0.0;
-        if (n < N && j < d) v = (double)K[(int64_t)n * d + j] * s * g;
-        Kt64[(int64_t)n * dp + j] = v;
-    }
-    if (Rt) {
-        for (int i = threadIdx.x; i < hp; i += 256) {
-            double v = 0.0;
-            if (n < N && i < h) {
-                const float src = zs_t[(int64_t)n * h + i] - Zc[(int64_t)n * h + i];
-                v = ((double)src * s) / layers_left * g;
-            }
-            Rt[(int64_t)n * hp + i] = v;
-        }
-    }
-}
-
-// Kt64[n][j] = double(K[n][j]) * s * g alone (zero padded to [Np][dp]): a retained key (emcid_session_retain_f64) has no
-// residual side; the conversion is prep_kr_kernel's, operation for operation
-__global__ __launch_bounds__(256) void prep_k_kernel(const float* __restrict__ K, int N, int d, double s, double* __restrict__ Kt64,
-                                                      int dp, double g) {
-    const int n = blockIdx.x;
-    for (int j = threadIdx.x; j < dp; j += 256) {
-        double v = 0.0;
-        if (n < N && j < d) v = (double)K[(int64_t)n * d + j] * s * g;
-        Kt64[(int64_t)n * dp + j] = v;
-    }
-}
-
-// The readout of a preserve step (emcid_session_step_norms_f64): one wave per output, four outputs per workgroup.
-//   o <  M              drift[o]        = || ZT[0:h, o] ||_2          (ZT = [Zp^T | Zk^T] [h][ldz]: column o, strided by ldz)
-//   M <= o < M + N      left[o - M]     = || ZT[0:h, o] ||_2
-//   M + N <= o          resid[o - M - N] = || Rt[o - M - N, 0:h] ||_2  (Rt [N][ldr])
-__global__ __launch_bounds__(256) void step_norms_kernel(const double* __restrict__ ZT, int64_t ldz, const double* __restrict__ Rt,
-                                                          int64_t ldr, int h, int M, int N, double* __restrict__ drift,
-                                                          double* __restrict__ left, double* __restrict__ resid) {
-    const int lane = threadIdx.x & 63;
-    const int o = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (o >= M + 2 * N) return;       // (whole waves leave: no lane of a wave that stays is missing from the shuffles)
-    double s = 0.0;
-    if (o < M + N) {
-        for (int i = lane; i < h; i += 64) {
-            const double v = ZT[(int64_t)i * ldz + o];
-            s += v * v;
-        }
-    } else {
-        const double* r = Rt + (int64_t)(o - M - N) * ldr;
-        for (int i = lane; i < h; i += 64) s += r[i] * r[i];
-    }
-    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
-    if (lane == 0) {
-        if (o < M) drift[o] = sqrt(s);
-        else if (o < M + N) left[o - M] = sqrt(s);
-        else resid[o - M - N] = sqrt(s);
-    }
-}
-
-// dst[j][0:dp] = src[idx[j]][0:dp] for j < n, zero for the padding rows n <= j < gridDim.x (emcid_session_release_f64: the kept rows
-// of Yp, gathered through the workspace because they overlap their destination).  One workgroup per row, double2; src, dst 16-byte
-// aligned, lds_ and dp even.  An index outside [0, rows) reads nothing: the row is zeroed.
-__global__ __launch_bounds__(256) void gather_rows_f64_kernel(const double* __restrict__ src, int64_t lds_, const int32_t* __restrict__ idx,
-                                                               int n, int rows, double* __restrict__ dst, int dp) {
-    const int j = blockIdx.x;
-    const int r = j < n ? idx[j] : -1;
-    const double2* s = r >= 0 && r < rows ? reinterpret_cast<const double2*>(src + (int64_t)r * lds_) : nullptr;
-    double2* o = reinterpret_cast<double2*>(dst + (int64_t)j * dp);
-    for (int c = threadIdx.x; c < dp / 2; c += 256) o[c] = s ? s[c] : make_double2(0.0, 0.0);
-}
-
-__global__ __launch_bounds__(256) void copy2d_f64_kernel(const double* __restrict__ src, int64_t lds_, double* __restrict__ dst,
-                                                          int64_t ldd, int rows, int cols, double scale = 1.0) {
-    const int r = blockIdx.x;
-    for (int c = threadIdx.x; c < cols; c += 256) dst[(int64_t)r * ldd + c] = src[(int64_t)r * lds_ + c] * scale;
-}
-
-// zero fill by kernel: a hipMemset node inside a captured graph binds the allocation object of capture time, which
-// goes stale when the caller's allocator recycles the address range; a kernel only carries the raw pointer
-__global__ __launch_bounds__(256) void zero_f64_kernel(double* __restrict__ p, int64_t n) {
-    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (; i < n; i += stride) p[i] = 0.0;
-}
-
-__global__ __launch_bounds__(256) void axpy_f32_kernel(float* __restrict__ W, const float* __restrict__ dW, int64_t n) {
-    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (; i < n; i += stride) W[i] += dW[i];
-}
-
-// W = W0 + float(U) ; dW = float(U)   (after the partial U of the concept shards were summed)
-__global__ __launch_bounds__(256) void apply_u_kernel(const double* __restrict__ U, const float* __restrict__ W0,
-                                                       float* __restrict__ W, float* __restrict__ dW, int64_t n) {
-    int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (; i < n; i += stride) {
-        const float f = (float)U[i];
-        if (dW) dW[i] = f;
-        if (W) W[i] = W0[i] + f;
-    }
-}
-
-// W = W0 + float(U), dW = float(U) with U[h][ldu] (the apply-only dual path leaves U with the padded leading dimension)
-__global__ __launch_bounds__(256) void apply_u2d_kernel(const double* __restrict__ U, int64_t ldu, const float* __restrict__ W0,
-                                                         float* __restrict__ W, float* __restrict__ dW, int d) {
-    const int i = blockIdx.x;
-    for (int j = threadIdx.x; j < d; j += 256) {
-        const float f = (float)U[(int64_t)i * ldu + j];
-        if (dW) dW[(int64_t)i * d + j] = f;
-        if (W) W[(int64_t)i * d + j] = W0[(int64_t)i * d + j] + f;
-    }
-}
 
 // ---- diagonal leaf: Cholesky of one NB x NB block + its inverse, one workgroup ---------------------------
 //
@@ -186,15 +37,6 @@ __device__ __forceinline__ double readlane_f64(double x, int lane) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(x), lane);
     const int hi = __builtin_amdgcn_readlane(__double2hiint(x), lane);
     return __hiloint2double(hi, lo);
-}
-
-__device__ __forceinline__ double rsqrt_f64(double d) {
-    double r = __builtin_amdgcn_rsq(d);
-    // two Newton steps: r <- r * (1.5 - 0.5 * d * r^2)
-    const double hd = 0.5 * d;
-    r = r * fma(-hd * r, r, 1.5);
-    r = r * fma(-hd * r, r, 1.5);
-    return r;
 }
 
 // one 16x16 output tile, K deep, operands fetched through address functors (doubles in LDS)
@@ -565,39 +407,8 @@ __global__ __launch_bounds__(LEAF_T) void chol_leaf_kernel(const double* __restr
     chol_leaf_body(A + blockIdx.x * s_mat, lda, L + blockIdx.x * s_mat, ldl, inv + blockIdx.x * s_inv, ldinv, info, col0, dbg, lds);
 }
 
-// A product that does NOT depend on the matrix being factored, cut into `nslices` K slices, one per leaf launch: the leaf
-// occupies ONE compute unit for ~36 us while the rest of the chip has (almost) nothing to do, so an independent GEMM of the
-// caller's rides along in the launches' other workgroups ("shadow").  Used by the dual solver for P = Yt X (X = inv(L) of
-// lam*C', lower triangular, stored [k][n]), which turns U = (Z^T Yt) X — a GEMM against the triangle AFTER the N x N solve, on
-// the critical path — into U = Z^T P.  C = A B with B(k, n) = 0 for k < n; 64 x 128 output tiles; a workgroup takes column tile
-// j and its mirror image NT-1-j (equal total depth for every workgroup) and contracts slice `slice` of each tile's own K range;
-// slice 0 stores, later slices add — launches of one stream are ordered and a tile belongs to one workgroup per launch, so the
-// sum order is fixed (bit-reproducible) and nothing is atomic.
-struct ShadowJob {
-    const double* A; int64_t lda;     // [M][K], K contiguous
-    const double* B; int64_t ldb;     // [K][N], N contiguous, zero for k < n
-    double* C; int64_t ldc;           // [M][N]
-    int M, N, K;
-    int wgs;                          // workgroups per launch: ceil(M / 64) * ceil(ceil(N / 128) / 2); 0 = no job
-    long long* stamps;                // diagnostic (usually null): per launch slice and workgroup [start, mid, end, kind]
-    int xcd_gx;                       // > 0: XCD-blocked tile assignment, the 8 XCDs as a xcd_gx x (8 / xcd_gx) grid (set by the launcher)
-    int nofast;                       // GemmShape.nofast for the shadow tiles (EMCID_GEMM_FAST=0)
-    int fuse_pair;                    // both tiles of a pair through one software pipeline (EMCID_SHADOW_FUSE, default 1)
-};
-
-// The explicit inverse of the factor, built ROW BLOCK BY ROW BLOCK inside the factorization's own launches (dual solver: XS =
-// inv(LS) is what turns Z = S^-1 R into two GEMMs).  Stored transposed, Xt[n][k] = X[k][n], so that both products of a step are
-// K-contiguous on both sides:
-//     leaf launch j  (j >= 1):  Tt [128 j, 128] = Xt[0:128j, 0:128j] L[j, 0:j]^T        (X of the leading j blocks is complete)
-//     spine launch j (j >= 0):  Xt[0:128j, j]  = -Tt inv(L_jj)^T,   Xt[j, j] = inv(L_jj)^T
-// i.e. X[j, 0:j] = -inv(L_jj) L[j, 0:j] X[0:j, 0:j].  Behind the last leaf only that block row's second product is left (one
-// small launch) where the recursive-halving build took six dependent ones (~70 us per layer at N = 1000).
-struct XrowJob {
-    double* Xt; int64_t ldx;      // [n, n] transposed inverse (every entry the consumers read is written here)
-    double* Tt;                   // [n, 128] scratch, leading dimension 128
-};
-inline long long* g_step_stamps = nullptr;      // set by emcid_debug_step_stamps
-constexpr int SH_BM = 64, SH_BN = 128;
+// ---- what rides in the leaf launches: the ShadowJob and XrowJob of spd_solve.h ------------------------------------------------
+static long long* g_step_stamps = nullptr;      // set by emcid_debug_step_stamps
 
 template <int SH_BK, int SH_PF>
 __device__ __forceinline__ void shadow_tile(const ShadowJob& sh, int bm, int bn, int slice, int nslices, double* smem) {
@@ -798,7 +609,7 @@ __device__ __forceinline__ void shadow_pair(const ShadowJob& sh, int s_, int sli
 
 // One launch = the leaf of block j (workgroup 0) AND the trailing update of step j-1 that the leaf does not depend on (the other
 // workgroups, one 128 x 128 tile each): on one in-order stream a leaf and the previous step's bulk cannot overlap as two kernels,
-// and as parallel graph branches they cost more than they save (see cholesky_lookahead) — as one grid they simply run side by side.
+// and as parallel graph branches they cost more than they save (see cholesky_impl) — as one grid they simply run side by side.
 // Behind those, sh.wgs workgroups of the caller's shadow product (slice `slice` of `nslices`).
 __global__ __launch_bounds__(LEAF_T) void chol_step_leaf_kernel(const double* __restrict__ A, int64_t lda, double* __restrict__ L,
                                                                  int64_t ldl, double* __restrict__ inv, int64_t ldinv, int* info,
@@ -1029,8 +840,6 @@ __global__ __launch_bounds__(256) void copy_inverse_transposed_kernel(const doub
 static inline double* inv_block(double* invw, int64_t J) { return invw + J * (int64_t)OB * OB; }
 static inline const double* inv_block(const double* invw, int64_t J) { return invw + J * (int64_t)OB * OB; }
 
-static int env_flag(const char* name, int dflt);
-
 // Completes inv(L_JJ) for every OB x OB diagonal block from the leaf's 128 x 128 inverses, two levels of
 //   inv([[A,0],[C,B]]) = [[A^-1, 0], [-B^-1 C A^-1, B^-1]]      (batched over the blocks)
 static void build_block_inverses(const double* L, int64_t dp, int64_t lda, double* invw, hipStream_t st, int nmat = 1,
@@ -1099,36 +908,12 @@ static void build_block_inverses(const double* L, int64_t dp, int64_t lda, doubl
     if (rem > 2 * NB) level_b(nfull, 1, (int)(rem - 2 * NB));
 }
 
-// Graphs are captured on an internal stream: the caller's stream may be the legacy default stream, which cannot capture.
-namespace {
-constexpr int MAX_DEVICES = 64;
-hipStream_t g_capture_stream[MAX_DEVICES] = {};      // one per device: a stream belongs to the device current at its creation
-std::mutex g_state_mutex;                           // graph cache + capture streams (entry points may be called from threads)
-int current_device() {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    return dev;
-}
-int capture_stream_init(int dev, hipStream_t* out) {
-    if (dev < 0 || dev >= MAX_DEVICES) return fail(EMCID_ERR_BAD_ARG, "emcid graph", "device ordinal out of range");
-    if (!g_capture_stream[dev] && hipStreamCreateWithFlags(&g_capture_stream[dev], hipStreamNonBlocking) != hipSuccess)
-        return fail(EMCID_ERR_HIP, "emcid graph", "hipStreamCreateWithFlags");
-    *out = g_capture_stream[dev];
-    return EMCID_OK;
-}
-}  // namespace
-
-static int env_flag(const char* name, int dflt) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
-
 // Two-level blocked Cholesky on one stream.  Outer blocks of OB = 512 columns are brought up to date LEFT-looking
 // (one GEMM against all previous columns, contraction depth = their count, so the Schur complement is read and
 // written once per 512 columns instead of once per 128); inside an outer block the classic right-looking
 // leaf -> panel -> trailing-update runs with NB = 128, its updates confined to the block's own <= 384 remaining columns.
-static int cholesky_serial(double* A, double* L, int64_t dp, int64_t lda, double* invw, int* info, hipStream_t st,
-                           int nbatch = 1, int64_t s_mat = 0, int64_t s_inv = 0) {
+int cholesky_serial(double* A, double* L, int64_t dp, int64_t lda, double* invw, int* info, hipStream_t st, int nbatch,
+                    int64_t s_mat, int64_t s_inv) {
     // nbatch independent matrices (A + b*s_mat, L + b*s_mat, invw + b*s_inv; s_inv == inv_doubles(dp)) are factored by
     // the same launches: every GEMM is batched over blockIdx.z and the leaf runs one workgroup per matrix.
     hipLaunchKernelGGL(zero_f64_kernel, dim3(1024), dim3(256), 0, st, invw, inv_doubles(dp) * nbatch);
@@ -1172,15 +957,14 @@ static int cholesky_serial(double* A, double* L, int64_t dp, int64_t lda, double
     return check_launch("emcid_cholesky_f64");
 }
 
-
 // ---- small Cholesky, two heterogeneous launches per 128 columns (n <= 2048) -------------------------------------------------------
 // Step j:   launch A_j = { leaf j }  +  { trailing update of step j-1 minus the block the leaf needs }
 //           launch B_j = { spine step j: L[j+1, j] and the next diagonal block }  +  { the rest of panel j }
 // Everything a launch contains depends on earlier LAUNCHES only, so the parts run side by side on the chip and the serial chain
 // per step is leaf + spine step + two kernel boundaries (~48 us) instead of leaf + panel + trailing update + three (~65 us) — with
-// one stream, i.e. without the parallel graph branches that sank cholesky_lookahead.
+// one stream, i.e. without parallel graph branches (see cholesky_impl).
 static int cholesky_fused_steps(double* A, double* L, int64_t n, int64_t lda, double* invw, int* info, hipStream_t st,
-                                const ShadowJob* shadow = nullptr, const XrowJob* xrow = nullptr) {
+                                const ShadowJob* shadow, const XrowJob* xrow) {
     const int nb = (int)(n / NB);
     hipLaunchKernelGGL(zero_f64_kernel, dim3(1024), dim3(256), 0, st, invw, inv_doubles(n));
     for (int j = 0; j < nb; ++j) {
@@ -1276,74 +1060,63 @@ static int cholesky_fused_steps(double* A, double* L, int64_t n, int64_t lda, do
     return check_launch("emcid_cholesky_f64");
 }
 
-// (A two-stream look-ahead schedule — spine leaf -> one panel block -> diagonal update on the caller's stream, bulk
-// panel/trailing on a side stream — was built and measured 6-11 % SLOWER, eager and as a graph: the leaf needs a
-// whole CU's LDS, so it cannot start while the bulk GEMM keeps every CU populated.  Kept serial.)
-static inline bool cholesky_takes_shadow(int64_t dp) {      // the schedule whose leaf launches can carry a ShadowJob
-    return dp <= 2048 && dp >= 2 * NB;
-}
-
-static int cholesky_impl(double* A, double* L, int64_t dp, int64_t lda, double* invw, int* info, hipStream_t st,
-                         const ShadowJob* shadow = nullptr, const XrowJob* xrow = nullptr) {
-    // (A look-ahead schedule on two streams — spine on the caller's, bulk on a side stream — was built in rounds 1-2 and lost:
-    // 13.3 -> 22.3 ms per device step inside the captured graph, every fork / join between capture streams costing ~70 us;
-    // removed in round 5, DESIGN.md "measured and dropped".)
+// Both schedules run on ONE stream.  (A look-ahead schedule on two streams — spine on the caller's, bulk on a side stream — was
+// built in rounds 1-2 and lost: 13.3 -> 22.3 ms per device step inside the captured graph, every fork / join between capture
+// streams costing ~70 us, and the leaf needs a whole CU's LDS, so it cannot start while the bulk GEMM keeps every CU populated;
+// removed in round 5, DESIGN.md "measured and dropped".)
+int cholesky_impl(double* A, double* L, int64_t dp, int64_t lda, double* invw, int* info, hipStream_t st, const ShadowJob* shadow,
+                  const XrowJob* xrow) {
     if (cholesky_takes_shadow(dp)) return cholesky_fused_steps(A, L, dp, lda, invw, info, st, shadow, xrow);
     if (shadow || xrow) return fail(EMCID_ERR_BAD_ARG, "cholesky_impl", "shadow / inverse job without the fused schedule");
     return cholesky_serial(A, L, dp, lda, invw, info, st);
 }
 
-// Bt[M, dp] := Bt (L L^T)^-1, right-looking over OB-wide column blocks: multiply by the inverted diagonal
-// block, then one rank-OB GEMM update of every remaining column (forward), the same backward.
-// forward half:  Yt L^T = Bt   (Bt is consumed as scratch)
-static void trsm_forward(const double* L, int64_t dp, int64_t lda, const double* invw, double* Bt, double* Yt, int M,
-                         int64_t ldb, hipStream_t st) {
-    const int nob = (int)((dp + OB - 1) / OB);
-    for (int J = 0; J < nob; ++J) {
-        const int64_t c = (int64_t)J * OB;
-        const int w = (int)((dp - c) < OB ? (dp - c) : OB);
-        const double* inv = inv_block(invw, J);
-        GemmShape a{Bt + c, ldb, inv, OB, M, w, w, 0};
+// Out[rows, n] = B (L^T)^-1 (forward) and Out = B L^-1 (backward) for a lower-triangular L [n, n], right-looking over blk-wide
+// column blocks: multiply by the inverted diagonal block (block J at inv + J blk^2, leading dimension blk), then one rank-blk
+// GEMM update of every remaining column.  B is consumed as scratch; n need not be a multiple of blk: the last block is the leading
+// w x w part of its inverse.  The solves against a covariance factor (blk = OB) and against a session's Lp (blk = NB) both run here.
+void trsm_forward(const double* L, int64_t ldl, int64_t n, int blk, const double* inv, double* B, int64_t ldb, double* Out,
+                  int64_t ldo, int rows, hipStream_t st) {
+    for (int64_t c = 0; c < n; c += blk) {
+        const int w = (int)((n - c) < blk ? (n - c) : blk);
+        GemmShape a{B + c, ldb, inv + (c / blk) * (int64_t)blk * blk, blk, rows, w, w, 0};
         a.tri = 1;   // B(k, n) = inv[n][k], zero for k > n
         {
             ScopedProf sp(KC_TRSM_DIAG, st);
-            launch_gemm_f64<true, true>(a, EpiAxpby{Yt + c, ldb, 1.0, 0.0}, st);
+            launch_gemm_f64<true, true>(a, EpiAxpby{Out + c, ldo, 1.0, 0.0}, st);
         }
-        const int m = (int)(dp - c - w);
+        const int m = (int)(n - c - w);
         if (m > 0) {
-            GemmShape b{Yt + c, ldb, L + (c + w) * lda + c, lda, M, m, w, 0};
+            GemmShape b{Out + c, ldo, L + (c + w) * ldl + c, ldl, rows, m, w, 0};
             ScopedProf sp(KC_TRSM_UPDATE, st);
-            launch_gemm_f64<true, true>(b, EpiAxpby{Bt + c + w, ldb, -1.0, 1.0}, st);
+            launch_gemm_f64<true, true>(b, EpiAxpby{B + c + w, ldb, -1.0, 1.0}, st);
         }
     }
 }
 
-// backward half:  Xt L = Yt   (Yt is consumed as scratch, Xt may be any buffer of the same shape)
-static void trsm_backward(const double* L, int64_t dp, int64_t lda, const double* invw, double* Yt, double* Xt, int M,
-                          int64_t ldb, hipStream_t st) {
-    const int nob = (int)((dp + OB - 1) / OB);
-    for (int J = nob - 1; J >= 0; --J) {
-        const int64_t c = (int64_t)J * OB;
-        const int w = (int)((dp - c) < OB ? (dp - c) : OB);
-        const double* inv = inv_block(invw, J);
-        GemmShape a{Yt + c, ldb, inv, OB, M, w, w, 0};
+void trsm_backward(const double* L, int64_t ldl, int64_t n, int blk, const double* inv, double* B, int64_t ldb, double* Out,
+                   int64_t ldo, int rows, hipStream_t st) {
+    for (int64_t c = (n - 1) / blk * blk; c >= 0; c -= blk) {
+        const int w = (int)((n - c) < blk ? (n - c) : blk);
+        GemmShape a{B + c, ldb, inv + (c / blk) * (int64_t)blk * blk, blk, rows, w, w, 0};
         a.tri = 2;   // B(k, n) = inv[k][n], zero for k < n
         {
             ScopedProf sp(KC_TRSM_DIAG, st);
-            launch_gemm_f64<true, false>(a, EpiAxpby{Xt + c, ldb, 1.0, 0.0}, st);
+            launch_gemm_f64<true, false>(a, EpiAxpby{Out + c, ldo, 1.0, 0.0}, st);
         }
         if (c > 0) {
-            GemmShape b{Xt + c, ldb, L + c * lda, lda, M, (int)c, w, 0};
+            GemmShape b{Out + c, ldo, L + c * ldl, ldl, rows, (int)c, w, 0};
             ScopedProf sp(KC_TRSM_UPDATE, st);
-            launch_gemm_f64<true, false>(b, EpiAxpby{Yt, ldb, -1.0, 1.0}, st);
+            launch_gemm_f64<true, false>(b, EpiAxpby{B, ldb, -1.0, 1.0}, st);
         }
     }
 }
 
-static int cholesky_solve_impl(const double* L, int64_t dp, int64_t lda, const double* invw, double* Bt, double* Yt,
-                               int64_t Mrows, int64_t ldb, hipStream_t st) {
-    trsm_forward(L, dp, lda, invw, Bt, Yt, (int)Mrows, ldb, st);
-    trsm_backward(L, dp, lda, invw, Yt, Bt, (int)Mrows, ldb, st);   // Xt written over Bt
+// Bt[M, dp] := Bt (L L^T)^-1 (Yt: scratch of the same shape), against the OB-block inverses of build_block_inverses
+int cholesky_solve_impl(const double* L, int64_t dp, int64_t lda, const double* invw, double* Bt, double* Yt, int64_t Mrows,
+                        int64_t ldb, hipStream_t st) {
+    trsm_forward(L, lda, dp, OB, invw, Bt, ldb, Yt, ldb, (int)Mrows, st);
+    trsm_backward(L, lda, dp, OB, invw, Yt, ldb, Bt, ldb, (int)Mrows, st);   // Xt written over Bt
     return check_launch("emcid_cholesky_solve_f64");
 }
 
@@ -1367,13 +1140,8 @@ __global__ __launch_bounds__(256) void copy_diag_inverse_kernel(const double* __
     for (int j = threadIdx.x; j < (hi < w ? hi : w); j += 256) dst[j] = (j <= i) ? src[j] : 0.0;
 }
 
-__global__ __launch_bounds__(256) void zero2d_f64_kernel(double* __restrict__ p, int64_t ld, int64_t s_batch, int cols) {
-    double* row = p + blockIdx.y * s_batch + (int64_t)blockIdx.x * ld;
-    for (int j = threadIdx.x; j < cols; j += 256) row[j] = 0.0;
-}
-
-static int build_full_inverse(const double* L, int64_t dp, int64_t lda, const double* invw, double* X, double* T, int nbatch,
-                              int64_t s_mat, int64_t s_inv, hipStream_t st) {
+int build_full_inverse(const double* L, int64_t dp, int64_t lda, const double* invw, double* X, double* T, int nbatch,
+                       int64_t s_mat, int64_t s_inv, hipStream_t st) {
     ScopedProf sp(KC_INV_BUILD, st);
     hipLaunchKernelGGL(copy_diag_inverse_kernel, dim3((unsigned)dp, (unsigned)nbatch), dim3(256), 0, st, invw, s_inv, X, lda, s_mat, dp);
     const int nob = (int)((dp + OB - 1) / OB);
@@ -1417,16 +1185,15 @@ static int build_full_inverse(const double* L, int64_t dp, int64_t lda, const do
 }
 
 // Both GEMMs against X contract over a triangular K range; they run as stream-K over 128x128 tiles (gemm_f64.h): the
-// (tile, K-step) space cut into 256 equal runs, whole tiles stored, the two partial tiles of a run added atomically
+// (tile, K-step) space cut into kStreamKWgs = 256 equal runs, whole tiles stored, the two partial tiles of a run added atomically
 // into a zeroed output.  Measured for 1024 x 3072 x 3072: 218 us (zeroing included) against 253 us for mirrored 32x64
 // tile pairs and 306 us for plain 64x64 tiles; 768 rows: 188 / 238 / 299 us (scripts/mb_tri.py).
-static const int kStreamKWgs = 256;
-
+//
 // With the interior fast path of the small-tile ring, mirrored PAIRS of 32 x 64 tiles (every workgroup contracts over the same
 // total depth, three 4-wave workgroups per compute unit, no split, no fix-up) beat the stream-K form whenever their count fills
 // the chip's 768 slots evenly (scripts/mb_tri_small.py, d = 3072, us stream-K / pairs: 1024 rows 187 / 172 and 195 / 177; 768
 // rows 146 / 161; 512 rows 104 / 118), and for very few rows on the backward product (128 rows: 114 / 80; 256: 98 / 81), where a
-// stream-K run is mostly fix-up.  EMCID_TRI_PAIRS=0 keeps stream-K everywhere.
+// stream-K run is mostly fix-up.
 static inline bool pairs_fill_the_chip(int rows, int64_t dp, bool backward) {
     const int64_t wgs = (int64_t)((rows + 31) / 32) * (((dp + 63) / 64 + 1) / 2);
     // (at most 128 rows: the stream-K form on 64 x 64 tiles is ahead — P = Yt X of a 100-concept edit 75 -> 54 us, inv_apply 0.51 -> 0.42 ms per call)
@@ -1442,8 +1209,7 @@ static inline bool few_rows_ksplit(int rows, int64_t dp) {
 }
 
 // Yt[rows, dp] = Kt[rows, dp] * X^T  (= Kt L^-T: the forward substitution as one GEMM)
-static void apply_inverse_forward(const double* X, int64_t dp, const double* Kt, double* Yt, int rows, hipStream_t st,
-                                  double* sk_work = nullptr) {
+void apply_inverse_forward(const double* X, int64_t dp, const double* Kt, double* Yt, int rows, hipStream_t st, double* sk_work) {
     ScopedProf sp(KC_INV_APPLY, st);
     GemmShape g{Kt, dp, X, dp, rows, (int)dp, (int)dp, 0};
     g.tri = 1;       // B(k, n) = X[n][k], zero for k > n
@@ -1466,8 +1232,8 @@ static void apply_inverse_forward(const double* X, int64_t dp, const double* Kt,
 }
 
 // C[rows, ncols] (f64, leading dimension ldc) = V[rows, dp] * X  (= V L^-1: the backward substitution as one GEMM)
-static void apply_inverse_backward(const double* X, int64_t dp, const double* V, int rows, int ncols, double* C, int64_t ldc,
-                                   hipStream_t st, double* sk_work = nullptr) {
+void apply_inverse_backward(const double* X, int64_t dp, const double* V, int rows, int ncols, double* C, int64_t ldc,
+                            hipStream_t st, double* sk_work) {
     ScopedProf sp(KC_INV_APPLY, st);
     GemmShape g{V, dp, X, dp, rows, ncols, (int)dp, 0};
     g.tri = 2;       // B(k, n) = X[k][n], zero for k < n
@@ -1487,239 +1253,9 @@ static void apply_inverse_backward(const double* X, int64_t dp, const double* V,
     launch_gemm_f64<true, false>(g, EpiAxpby{C, ldc, 1.0, 0.0}, st, 2);
 }
 
-// layout of the covariance-factor workspace (emcid_factor_cov_f64): [M | L | 512-block inverses | X = inv(L)] x n_layers
-static inline const double* cov_inverse(const void* cov_factor_ws, int64_t n_layers, int64_t dp, int64_t layer) {
-    return (const double*)cov_factor_ws + n_layers * (2 * dp * dp + inv_doubles(dp)) + layer * dp * dp;
-}
-
-// ---- factor + solve as one cached hipGraph -----------------------------------------------------------------------
-// The ~100 launches of one layer's Cholesky + block-inverse build + triangular solves take only workspace
-// pointers and sizes, so the whole chain (is captured once
-// per (workspace, shape) and replayed: dependent-kernel boundaries inside a graph cost ~1.2 us instead of a host
-// launch each.  Not used while per-kernel event timing is on (the events would be recorded at capture time).
-namespace {
-struct GraphKey {
-    const void* ptr[8];
-    int64_t num[6];
-    int64_t dev;          // device the launches were captured for (filled in by with_graph)
-    bool operator==(const GraphKey& o) const { return memcmp(this, &o, sizeof(GraphKey)) == 0; }
-};
-struct GraphSlot { GraphKey key; hipGraphExec_t exec; hipGraph_t graph; uint64_t used; };
-constexpr int GRAPH_SLOTS = 64;     // (32 was one bench process short: its SDXL record re-captured graphs in every call once the other records had filled the cache)
-GraphSlot g_graphs[GRAPH_SLOTS];
-int g_graph_n = 0;
-uint64_t g_graph_clock = 0;
-
-GraphKey make_key(int tag, std::initializer_list<const void*> ptrs, std::initializer_list<int64_t> nums) {
-    GraphKey k;
-    memset(&k, 0, sizeof(k));
-    int i = 0;
-    for (const void* p : ptrs) k.ptr[i++] = p;
-    i = 0;
-    k.num[5] = tag;
-    for (int64_t n : nums) k.num[i++] = n;
-    return k;
-}
-}  // namespace
-
-// Runs `body(stream)` — a chain of launches whose arguments are fully determined by `key` — as a cached hipGraph.
-template <class F>
-static int with_graph(const GraphKey& key_in, hipStream_t st, F&& body) {
-    static const int use_graph = env_flag("EMCID_GRAPH", 1);
-    if (!use_graph || g_prof_mask != 0) return body(st);
-    std::lock_guard<std::mutex> lock(g_state_mutex);
-    GraphKey key = key_in;
-    key.dev = current_device();     // the caller made the buffers' device current (emcid_amd/hip.py does; see emcid_hip.h)
-    GraphSlot* slot = nullptr;
-    for (int i = 0; i < g_graph_n; ++i)
-        if (g_graphs[i].key == key) { slot = &g_graphs[i]; break; }
-    if (!slot) {
-        hipStream_t cap = nullptr;
-        EMCID_TRY(capture_stream_init((int)key.dev, &cap));
-        if (hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal) != hipSuccess)
-            return fail(EMCID_ERR_HIP, "emcid graph", "hipStreamBeginCapture");
-        const int rc = body(cap);
-        hipGraph_t graph = nullptr;
-        const hipError_t ec = hipStreamEndCapture(cap, &graph);
-        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (ec != hipSuccess || !graph) return fail(EMCID_ERR_HIP, "emcid graph", "hipStreamEndCapture");
-        hipGraphExec_t exec = nullptr;
-        if (hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-            (void)hipGraphDestroy(graph);
-            return fail(EMCID_ERR_HIP, "emcid graph", "hipGraphInstantiate");
-        }
-        if (g_graph_n < GRAPH_SLOTS) {
-            slot = &g_graphs[g_graph_n++];
-        } else {   // evict the least recently used graph
-            slot = &g_graphs[0];
-            for (int i = 1; i < GRAPH_SLOTS; ++i)
-                if (g_graphs[i].used < slot->used) slot = &g_graphs[i];
-            (void)hipDeviceSynchronize();   // the evicted graph may still be executing
-            (void)hipGraphExecDestroy(slot->exec);
-            (void)hipGraphDestroy(slot->graph);
-        }
-        slot->key = key; slot->exec = exec; slot->graph = graph;
-    }
-    slot->used = ++g_graph_clock;
-    if (hipGraphLaunch(slot->exec, st) != hipSuccess) return fail(EMCID_ERR_HIP, "emcid graph", "hipGraphLaunch");
-    return EMCID_OK;
-}
-
-static int factor_and_solve(double* A, double* L, int64_t dp, int64_t lda, double* invw, int* info, double* B, double* Y,
-                            int64_t rows, int64_t ldb, hipStream_t st) {
-    return with_graph(make_key(1, {A, L, invw, info, B, Y}, {dp, lda, rows, ldb}), st, [&](hipStream_t s) {
-        EMCID_TRY(cholesky_impl(A, L, dp, lda, invw, info, s));
-        return cholesky_solve_impl(L, dp, lda, invw, B, Y, rows, ldb, s);
-    });
-}
-
-// ---- dual (Woodbury) solver -----------------------------------------------------------------------------------------
-// A = M + Kt^T Kt with M = lam*C' independent of the concepts.  Then  Xt = Kt A^-1 = (I + Pt Kt^T)^-1 Pt,  Pt = Kt M^-1:
-// the d x d factorization is of M only — done for ALL edited layers at once, batched, before (and concurrently with)
-// the forward pass — and each layer factors just the Np x Np matrix S = I + Pt Kt^T.
-
-// M[l] = lam * double(fl32(fl32(C[l]*cw)/0.5f)) on the lower triangle, identity on the padding (as EpiAssemble)
-struct CovPtrs { const float* c[32]; };
-__global__ __launch_bounds__(256) void scale_cov_kernel(CovPtrs cov, int d, int dp, double lam, float cw, double* __restrict__ M,
-                                                         int64_t s_mat) {
-    const int l = blockIdx.y;
-    const int i = blockIdx.x;
-    const float* C = cov.c[l];
-    double* row = M + l * s_mat + (int64_t)i * dp;
-    for (int j = threadIdx.x; j <= i; j += 256) {
-        double v;
-        if (i < d) {
-            const float c1 = C[(int64_t)i * d + j] * cw;
-            v = lam * (double)(c1 / 0.5f);
-        } else {
-            v = (i == j) ? 1.0 : 0.0;
-        }
-        row[j] = v;
-    }
-}
-
-
-// S = I (full square): start value of the split-K accumulation S += Yt Yt^T
-__global__ __launch_bounds__(256) void eye_f64_kernel(double* __restrict__ S, int n) {
-    const int i = blockIdx.x;
-    for (int j = threadIdx.x; j < n; j += 256) S[(int64_t)i * n + j] = (i == j) ? 1.0 : 0.0;
-}
-
-// S[Np, Np] = I + P Q^T on the lower tiles, K = dp deep.  Np x Np is too few output tiles for the chip, so the
-// contraction is split over workgroups that add their partials into the identity with f64 atomics.
-static void assemble_dual_system(const double* P, const double* Q, int64_t dp, double* S, int Np, hipStream_t st,
-                                 double* sk_work = nullptr) {
-    ScopedProf sp(KC_ASSEMBLE, st);
-    GemmShape g{P, dp, Q, dp, Np, Np, (int)dp, 1};
-    // S = I + P Q^T written once per tile, no identity pass (unless there are more tiles than ticket counters)
-    if (Np >= 512 && sk_work && launch_gemm_f64_streamk2<true, true>(g, EpiAxpby{S, Np, 1.0, 0.0}, st, kStreamKWgs, sk_work, 1.0))
-        return;
-    hipLaunchKernelGGL(eye_f64_kernel, dim3((unsigned)Np), dim3(256), 0, st, S, Np);
-    const int kt = (int)(dp / 16);
-    g.ksplit = kt >= 64 ? 4 : kt >= 32 ? 2 : 1;
-    launch_gemm_f64<true, true>(g, EpiAxpby{S, Np, 1.0, 1.0}, st, Np >= 512 ? 1 : 2);
-}
-
-__global__ __launch_bounds__(256) void transpose_f64_kernel(const double* __restrict__ src, int64_t lds_, double* __restrict__ dst,
-                                                             int64_t ldd, int rows, int cols) {
-    __shared__ double tile[32][33];
-    const int bx = blockIdx.x * 32, by = blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int r = ty; r < 32; r += 8)
-        tile[r][tx] = (by + r < rows && bx + tx < cols) ? src[(int64_t)(by + r) * lds_ + bx + tx] : 0.0;
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8)
-        if (bx + r < cols && by + tx < rows) dst[(int64_t)(bx + r) * ldd + by + tx] = tile[tx][r];
-}
-
-struct DualWorkspace {
-    int64_t Np, dp, hp;
-    int64_t off_K, off_P, off_Y, off_R, off_S, off_LS, off_invS, off_PT, off_Y2, off_V, off_U, off_SK, total;   // doubles
-    DualWorkspace(int64_t N, int64_t d, int64_t h) {
-        Np = round_up(N, NB);
-        dp = round_up(d, NB);
-        hp = round_up(h, 2);
-        int64_t o = 0;
-        off_K = o; o += Np * dp;
-        off_P = o; o += Np * dp;
-        off_Y = o; o += Np * dp;
-        off_R = o; o += Np * hp;
-        off_S = o; o += Np * Np;
-        off_LS = o; o += Np * Np;
-        off_invS = o; o += inv_doubles(Np);
-        off_PT = o; o += dp * Np;
-        off_Y2 = o; o += dp * Np;
-        off_V = o; o += hp * dp;
-        off_U = o; o += hp * dp;
-        off_SK = o; o += streamk_workspace_doubles(kStreamKWgs);      // partial-tile slots + ticket counters (zero between launches)
-        off_XT = o; o += Np * Np;                                     // XrowJob: inv(LS)^T ...
-        off_TT = o; o += Np * NB;                                     // ... and its per-step scratch
-        total = o;
-    }
-    int64_t off_XT, off_TT;
-};
-
-struct EditWorkspace {
-    int64_t Np, dp, hp;
-    int64_t off_A, off_L, off_inv, off_B, off_Y, off_R, total;  // in doubles
-    EditWorkspace(int64_t N, int64_t d, int64_t h) {
-        Np = round_up(N, NPAD);
-        dp = round_up(d, NB);
-        hp = round_up(h, 2);
-        int64_t o = 0;
-        off_A = o; o += dp * dp;
-        off_L = o; o += dp * dp;
-        off_inv = o; o += inv_doubles(dp);
-        off_B = o; o += Np * dp;
-        off_Y = o; o += Np * dp;
-        off_R = o; o += Np * hp;
-        total = o;
-    }
-};
-
-// ---- dual solver with a preserved key set (edit sessions) ---------------------------------------------------------------------
-// State of a layer: Yp [M, dp] (the Yt rows of every earlier step), Lp = chol(I + Yp Yp^T) [M, M], and the inverses of Lp's
-// 128 x 128 diagonal tiles (they keep the two solves against Lp GEMM-shaped).  A step appends N rows to all three.
-
-// Inverse of one diagonal tile of Lp, extended by the rows a step appended: column j of inv(L) only depends on column j
-// (x_ij = (delta_ij - sum_{j <= k < i} L_ik x_kj) / L_ii), so 16 columns go to one wave — 4 lanes per column share the k sum —
-// and the rows [0, r0) the state already holds are read back, not recomputed.  grid (tiles touched by rows [M, MN), 8).
-__global__ __launch_bounds__(64) void tile_inverse_extend_kernel(const double* __restrict__ Lp, int64_t ldl, double* __restrict__ T,
-                                                                  int M, int MN) {
-    const int J = M / NB + blockIdx.x, c = J * NB;
-    const int r0 = M > c ? M - c : 0, r1 = (MN - c) < NB ? (MN - c) : NB;
-    const int lane = threadIdx.x, jl = lane & 15, part = lane >> 4, j = blockIdx.y * 16 + jl;
-    __shared__ double Xs[NB][17];
-    double* Tt = T + (int64_t)J * NB * NB;
-    for (int i = part; i < r0; i += 4) Xs[i][jl] = Tt[i * NB + j];
-    __syncthreads();
-    const double* Lt = Lp + (int64_t)c * ldl + c;
-    for (int i = r0; i < r1; ++i) {
-        const double* Li = Lt + (int64_t)i * ldl;
-        double s = 0.0;
-        for (int k = j + part; k < i; k += 4) s += Li[k] * Xs[k][jl];
-        s += __shfl_xor(s, 16);
-        s += __shfl_xor(s, 32);
-        const double x = j > i ? 0.0 : ((j == i ? 1.0 : 0.0) - s) / Li[i];
-        if (part == 0) {
-            Xs[i][jl] = x;
-            Tt[i * NB + j] = x;
-        }
-        __syncthreads();
-    }
-}
-
-// Lp[M + i][M + j] = LS[i][j] on and below the diagonal, zero above it (i, j < N)
-__global__ __launch_bounds__(256) void append_factor_kernel(const double* __restrict__ LS, int64_t lds_, double* __restrict__ Lp,
-                                                             int64_t ldl, int M, int N) {
-    const int i = blockIdx.x;
-    double* row = Lp + (int64_t)(M + i) * ldl + M;
-    for (int j = threadIdx.x; j < N; j += 256) row[j] = j <= i ? LS[(int64_t)i * lds_ + j] : 0.0;
-}
-
 // T += P P^T - Q Q^T on the lower 32 x 64 tiles in ONE launch: the contraction runs over the concatenation [P | Q] with a sign per
 // K range.  The first `zpos` z-slices split P's depth, the others Q's; every slice adds its partial with f64 atomics into T,
-// which the caller has set to the identity.
+// which the caller has set to the identity.  (Here, not with its only caller in session.hip: it inlines the GEMM tile.)
 __global__ __launch_bounds__(256) void syrk_signed_kernel(GemmShape pos, GemmShape neg, EpiAxpby epi, int zpos) {
     using TA = OpTile<true, 32, 16>;
     using TB = OpTile<true, 64, 16>;
@@ -1731,9 +1267,8 @@ __global__ __launch_bounds__(256) void syrk_signed_kernel(GemmShape pos, GemmSha
     gemm_f64_tile<true, true, 32, 64, 16, 2, 2>(p, epi, (int)blockIdx.y, (int)blockIdx.x, first ? (int)blockIdx.z : (int)blockIdx.z - zpos, smem);
 }
 
-// S[Np, Np] = I + Yk Yk^T - Lkp Lkp^T (lower tiles; rows / columns >= N stay those of the identity)
-static void assemble_schur_system(const double* Yk, int64_t ldy, int64_t dp, const double* Lkp, int64_t ldl, int64_t M, double* S,
-                                  int N, int Np, hipStream_t st) {
+void assemble_schur_system(const double* Yk, int64_t ldy, int64_t dp, const double* Lkp, int64_t ldl, int64_t M, double* S, int N,
+                           int Np, hipStream_t st) {
     ScopedProf sp(KC_ASSEMBLE, st);
     hipLaunchKernelGGL(eye_f64_kernel, dim3((unsigned)Np), dim3(256), 0, st, S, Np);
     GemmShape pos{Yk, ldy, Yk, ldy, N, N, (int)dp, 1};
@@ -1748,164 +1283,8 @@ static void assemble_schur_system(const double* Yk, int64_t ldy, int64_t dp, con
                        st, pos, neg, epi, zpos);
 }
 
-// Lkp[rows, M] = B Lp^-T by 128-wide column tiles against the kept tile inverses (B is consumed as scratch); M need not be a
-// multiple of 128: the last tile is the leading w x w part of its inverse
-static void trsm_tiles_forward(const double* Lp, int64_t ldl, const double* tinv, int64_t M, double* B, int64_t ldb, double* Out,
-                               int64_t ldo, int rows, hipStream_t st) {
-    for (int64_t c = 0; c < M; c += NB) {
-        const int w = (int)((M - c) < NB ? (M - c) : NB);
-        GemmShape a{B + c, ldb, tinv + (c / NB) * (int64_t)NB * NB, NB, rows, w, w, 0};
-        a.tri = 1;   // B(k, n) = inv[n][k], zero for k > n
-        {
-            ScopedProf sp(KC_TRSM_DIAG, st);
-            launch_gemm_f64<true, true>(a, EpiAxpby{Out + c, ldo, 1.0, 0.0}, st);
-        }
-        const int m = (int)(M - c - w);
-        if (m > 0) {
-            GemmShape b{Out + c, ldo, Lp + (c + w) * ldl + c, ldl, rows, m, w, 0};
-            ScopedProf sp(KC_TRSM_UPDATE, st);
-            launch_gemm_f64<true, true>(b, EpiAxpby{B + c + w, ldb, -1.0, 1.0}, st);
-        }
-    }
-}
-
-// Out[rows, M] = G Lp^-1, the same backward (G is consumed as scratch)
-static void trsm_tiles_backward(const double* Lp, int64_t ldl, const double* tinv, int64_t M, double* G, int64_t ldg, double* Out,
-                                int64_t ldo, int rows, hipStream_t st) {
-    for (int64_t c = (M - 1) / NB * NB; c >= 0; c -= NB) {
-        const int w = (int)((M - c) < NB ? (M - c) : NB);
-        GemmShape a{G + c, ldg, tinv + (c / NB) * (int64_t)NB * NB, NB, rows, w, w, 0};
-        a.tri = 2;   // B(k, n) = inv[k][n], zero for k < n
-        {
-            ScopedProf sp(KC_TRSM_DIAG, st);
-            launch_gemm_f64<true, false>(a, EpiAxpby{Out + c, ldo, 1.0, 0.0}, st);
-        }
-        if (c > 0) {
-            GemmShape b{Out + c, ldo, Lp + c * ldl, ldl, rows, (int)c, w, 0};
-            ScopedProf sp(KC_TRSM_UPDATE, st);
-            launch_gemm_f64<true, false>(b, EpiAxpby{G, ldg, -1.0, 1.0}, st);
-        }
-    }
-}
-
-// the blocks of a workspace that the key half of a step works on (session_append_rows)
-struct KeyHalf {
-    double *Yt, *S, *LS, *invS, *XT, *TT, *B;
-    int64_t dp, Np, cp;
-};
-
-struct PreserveWorkspace {
-    DualWorkspace dual;
-    int64_t cp, off_B, off_ZT, off_G, total;   // doubles
-    PreserveWorkspace(int64_t N, int64_t d, int64_t h, int64_t capacity) : dual(N, d, h) {
-        cp = round_up(capacity, NB);
-        int64_t o = dual.total;
-        off_B = o; o += dual.Np * cp;        // B = Yk Yp^T, consumed by the forward solve
-        off_ZT = o; o += dual.hp * cp;       // [Zp^T | Zk^T]
-        off_G = o; o += dual.hp * cp;        // -(Zk^T Lkp), consumed by the backward solve
-        total = o;
-    }
-    KeyHalf key_half(double* base) const {
-        return {base + dual.off_Y, base + dual.off_S, base + dual.off_LS, base + dual.off_invS, base + dual.off_XT, base + dual.off_TT,
-                base + off_B, dual.dp, dual.Np, cp};
-    }
-};
-
-// workspace of emcid_session_retain_f64: the key half of a PreserveWorkspace (no Rt, RT, Y2, V, U, ZT, G)
-struct RetainWorkspace {
-    int64_t Np, dp, cp;
-    int64_t off_K, off_Y, off_S, off_LS, off_invS, off_SK, off_XT, off_TT, off_B, total;   // doubles
-    RetainWorkspace(int64_t N, int64_t d, int64_t capacity) {
-        Np = round_up(N, NB);
-        dp = round_up(d, NB);
-        cp = round_up(capacity, NB);
-        int64_t o = 0;
-        off_K = o; o += Np * dp;
-        off_Y = o; o += Np * dp;
-        off_S = o; o += Np * Np;
-        off_LS = o; o += Np * Np;
-        off_invS = o; o += inv_doubles(Np);
-        off_SK = o; o += streamk_workspace_doubles(kStreamKWgs);
-        off_XT = o; o += Np * Np;
-        off_TT = o; o += Np * NB;
-        off_B = o; o += Np * cp;
-        total = o;
-    }
-    KeyHalf key_half(double* base) const {
-        return {base + off_Y, base + off_S, base + off_LS, base + off_invS, base + off_XT, base + off_TT, base + off_B, dp, Np, cp};
-    }
-};
-
-// what the session entries ask of the caller's state (Yp, Lp, tile inverses) for N rows behind row M
-static bool session_state_ok(int64_t M, int64_t N, int64_t d, const double* Yp, int64_t ldy, const double* Lp, int64_t ldl,
-                             const double* tile_inv, int64_t capacity) {
-    return M >= 0 && M + N <= capacity && capacity < (int64_t)1 << 30 && ldy >= round_up(d, NB) && ldy % 2 == 0 && ldl >= capacity &&
-           ldl % 2 == 0 && aligned16(Yp) && aligned16(Lp) && aligned16(tile_inv);
-}
-
-// The key half of a step behind row M, from N rows that already are in factor coordinates (k.Yt [Np][dp]): the copy into Yp,
-// B = Yk Yp^T, Lkp = B Lp^-T, T = I + Yk Yk^T - Lkp Lkp^T, its Cholesky (the explicit inverse XS = inv(LS) riding in the
-// factorization's launches as an XrowJob, transposed, when the fused schedule runs), the append and the tile inverses.  A preserve
-// step, a retain list and a release all run it.
-static int session_append_rows(const KeyHalf& k, int64_t N, double* Yp, int64_t ldy, double* Lp, int64_t ldl, double* tile_inv,
-                               int64_t M, int* info_dev, hipStream_t st, const char* who) {
-    const int64_t dp = k.dp, Np = k.Np, cp = k.cp;
-    double* Yk = Yp + M * ldy;
-    double* Lkp = Lp + M * ldl;
-    hipLaunchKernelGGL(copy2d_f64_kernel, dim3((unsigned)N), dim3(256), 0, st, k.Yt, dp, Yk, ldy, (int)N, (int)dp, 1.0);
-    if (M > 0) {
-        // B = Yk Yp^T: few output tiles, dp deep — the contraction is split, the partials added into zeros
-        hipLaunchKernelGGL(zero2d_f64_kernel, dim3((unsigned)N, 1u), dim3(256), 0, st, k.B, cp, (int64_t)0, (int)M);
-        {
-            ScopedProf sp(KC_ASSEMBLE, st);
-            GemmShape g{Yk, ldy, Yp, ldy, (int)N, (int)M, (int)dp, 0};
-            launch_gemm_f64<true, true>(g, EpiAxpby{k.B, cp, 1.0, 1.0}, st);
-        }
-        trsm_tiles_forward(Lp, ldl, tile_inv, M, k.B, cp, Lkp, ldl, (int)N, st);
-    }
-    assemble_schur_system(Yk, ldy, dp, Lkp, ldl, M, k.S, (int)N, (int)Np, st);
-    const XrowJob xj{k.XT, Np, k.TT};
-    EMCID_TRY(cholesky_impl(k.S, k.LS, Np, Np, k.invS, info_dev, st, nullptr, cholesky_takes_shadow(Np) ? &xj : nullptr));
-    hipLaunchKernelGGL(append_factor_kernel, dim3((unsigned)N), dim3(256), 0, st, k.LS, Np, Lp, ldl, (int)M, (int)N);
-    {
-        ScopedProf sp(KC_INV_BLOCK, st);
-        const unsigned tiles = (unsigned)((M + N - 1) / NB - M / NB + 1);
-        hipLaunchKernelGGL(tile_inverse_extend_kernel, dim3(tiles, NB / 16), dim3(64), 0, st, Lp, ldl, tile_inv, (int)M, (int)(M + N));
-    }
-    return check_launch(who);
-}
-
-// RT[h, Np] = Rt^T, then RT := Z^T = RT S^-1 for S = LS LS^T (Y2 [h, Np] is scratch).  As block substitution the solve is 6
-// dependent launches on h rows (~140 us at N = 1000, latency-bound); against an explicit XS = inv(LS) it is two GEMMs against a
-// triangle, Z^T = (RT XS^T) XS.  XT: XS transposed, as it rode in the factorization (XrowJob), or nullptr when the fused schedule
-// did not run.  Then XS is built into `full_inv` [Np, Np] (the callers pass S, which the factorization has consumed) up to
-// Np = 4096; beyond that, or without `full_inv`, the substitution stays.
-static int solve_schur_rhs(const double* R, int64_t hp, int64_t h, int64_t Np, const double* LS, const double* invS, const double* XT,
-                           double* full_inv, double* RT, double* Y2, hipStream_t st) {
-    hipLaunchKernelGGL(transpose_f64_kernel, dim3((unsigned)((hp + 31) / 32), (unsigned)(Np / 32)), dim3(256), 0, st, R, hp, RT, Np,
-                       (int)Np, (int)hp);
-    if (XT) {
-        ScopedProf sp(KC_TRSM_DIAG, st);
-        GemmShape f{RT, Np, XT, Np, (int)h, (int)Np, (int)Np, 0};
-        f.tri = 1; f.pair = 1;       // B(k, n) = XS[n][k] = Xt[k][n], zero for k > n
-        launch_gemm_f64<true, false>(f, EpiAxpby{Y2, Np, 1.0, 0.0}, st);
-        GemmShape b{Y2, Np, XT, Np, (int)h, (int)Np, (int)Np, 0};
-        b.tri = 2; b.pair = 1;       // B(k, n) = XS[k][n] = Xt[n][k], zero for k < n
-        launch_gemm_f64<true, true>(b, EpiAxpby{RT, Np, 1.0, 0.0}, st);
-    } else if (full_inv && Np <= 4096) {
-        EMCID_TRY(build_full_inverse(LS, Np, Np, invS, full_inv, Y2, 1, 0, 0, st));
-        ScopedProf sp(KC_TRSM_DIAG, st);
-        GemmShape f{RT, Np, full_inv, Np, (int)h, (int)Np, (int)Np, 0};
-        f.tri = 1; f.pair = 1;       // B(k, n) = XS[n][k], zero for k > n
-        launch_gemm_f64<true, true>(f, EpiAxpby{Y2, Np, 1.0, 0.0}, st);
-        GemmShape b{Y2, Np, full_inv, Np, (int)h, (int)Np, (int)Np, 0};
-        b.tri = 2; b.pair = 1;       // B(k, n) = XS[k][n], zero for k < n
-        launch_gemm_f64<true, false>(b, EpiAxpby{RT, Np, 1.0, 0.0}, st);
-    } else {
-        EMCID_TRY(cholesky_solve_impl(LS, Np, Np, invS, RT, Y2, h, Np, st));
-    }
-    return EMCID_OK;
-}
+// ---- the library's instantiations of the fp64 GEMM launchers, and through them of the kernels (see spd_solve.h) -------------
+EMCID_GEMM_F64_INSTANCES(template)
 
 }  // namespace emcid
 
@@ -1913,152 +1292,12 @@ using namespace emcid;
 
 extern "C" {
 
-int emcid_abi_version(void) { return EMCID_ABI_VERSION; }
-
-int emcid_profile_enable(unsigned class_mask) {
-    if (class_mask && !g_prof_init) {
-        for (int i = 0; i < PROF_MAX; ++i)
-            for (int j = 0; j < 2; ++j)
-                if (hipEventCreate(&g_prof_ev[i][j]) != hipSuccess) return fail(EMCID_ERR_HIP, __func__, "hipEventCreate");
-        g_prof_init = true;
-    }
-    g_prof_mask = class_mask;
-    g_prof_n = 0;
-    return EMCID_OK;
-}
-
-int emcid_profile_collect(double* ms_per_class, int64_t* launches_per_class, int n_classes) {
-    EMCID_CHECK_ARG(ms_per_class && launches_per_class && n_classes >= KC_COUNT);
-    for (int c = 0; c < n_classes; ++c) { ms_per_class[c] = 0.0; launches_per_class[c] = 0; }
-    for (int i = 0; i < g_prof_n; ++i) {
-        if (hipEventSynchronize(g_prof_ev[i][1]) != hipSuccess) return fail(EMCID_ERR_HIP, __func__, "hipEventSynchronize");
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, g_prof_ev[i][0], g_prof_ev[i][1]) != hipSuccess)
-            return fail(EMCID_ERR_HIP, __func__, "hipEventElapsedTime");
-        ms_per_class[g_prof_cls[i]] += ms;
-        launches_per_class[g_prof_cls[i]] += 1;
-    }
-    const int dropped = (g_prof_n >= PROF_MAX) ? 1 : 0;
-    g_prof_n = 0;
-    return dropped ? fail(EMCID_ERR_WORKSPACE, __func__, "event pool exhausted; enable fewer classes") : EMCID_OK;
-}
-const char* emcid_last_error(void) { return g_last_error; }
-
-int emcid_dgemm_f64(int ta, int tb, int64_t M, int64_t N, int64_t K, double alpha, const double* A, int64_t lda,
-                    const double* B, int64_t ldb, double beta, double* C, int64_t ldc, void* stream) {
-    EMCID_CHECK_ARG(M > 0 && N > 0 && K > 0 && A && B && C);
-    EMCID_CHECK_ARG(aligned16(A) && aligned16(B) && (lda % 2 == 0) && (ldb % 2 == 0));
-    EMCID_CHECK_ARG(M < (1 << 30) && N < (1 << 30) && K < (1 << 30));
-    hipStream_t st = (hipStream_t)stream;
-    GemmShape p{A, lda, B, ldb, (int)M, (int)N, (int)K, 0};
-    EpiAxpby e{C, ldc, alpha, beta};
-    ScopedProf sp(KC_DGEMM, st);
-    // ta/tb == 0: K contiguous ([rows][K]); 1: rows contiguous ([K][rows])
-    if (ta == 0 && tb == 0) launch_gemm_f64<true, true>(p, e, st);
-    else if (ta == 0 && tb == 1) launch_gemm_f64<true, false>(p, e, st);
-    else if (ta == 1 && tb == 0) launch_gemm_f64<false, true>(p, e, st);
-    else launch_gemm_f64<false, false>(p, e, st);
-    EMCID_CHECK_LAUNCH();
-    return EMCID_OK;
-}
-
-int emcid_dgemm_ex_f64(int ta, int tb, int64_t M, int64_t N, int64_t K, double alpha, const double* A, int64_t lda,
-                       const double* B, int64_t ldb, double beta, double* C, int64_t ldc, int flags, int cfg, int ksplit,
-                       void* stream) {
-    EMCID_CHECK_ARG(M > 0 && N > 0 && K > 0 && A && B && C);
-    EMCID_CHECK_ARG(aligned16(A) && aligned16(B) && (lda % 2 == 0) && (ldb % 2 == 0));
-    EMCID_CHECK_ARG(M < (1 << 30) && N < (1 << 30) && K < (1 << 30) && cfg >= -1 && cfg <= 2 && (flags & ~63) == 0);
-    EMCID_CHECK_ARG(ksplit == 0 || beta == 1.0);
-    hipStream_t st = (hipStream_t)stream;
-    GemmShape p{A, lda, B, ldb, (int)M, (int)N, (int)K, (flags >> 4) & 1};
-    p.tri = flags & 15;
-    p.pair = (flags >> 5) & 1;
-    if (ksplit > 0) p.ksplit = ksplit;
-    if (ksplit < 0) p.kchunk = -ksplit;
-    EpiAxpby e{C, ldc, alpha, beta};
-    ScopedProf sp(KC_DGEMM, st);
-    if (ta == 0 && tb == 0) launch_gemm_f64<true, true>(p, e, st, cfg);
-    else if (ta == 0 && tb == 1) launch_gemm_f64<true, false>(p, e, st, cfg);
-    else if (ta == 1 && tb == 0) launch_gemm_f64<false, true>(p, e, st, cfg);
-    else launch_gemm_f64<false, false>(p, e, st, cfg);
-    EMCID_CHECK_LAUNCH();
-    return EMCID_OK;
-}
-
-int64_t emcid_streamk_workspace_bytes(int wgs) { return wgs > 0 ? streamk_workspace_doubles(wgs) * (int64_t)sizeof(double) : 0; }
-
-int emcid_dgemm_streamk_f64(int tb, int64_t M, int64_t N, int64_t K, double alpha, const double* A, int64_t lda, const double* B,
-                            int64_t ldb, double* C, int64_t ldc, int flags, int wgs, double diag_add, void* workspace,
-                            int64_t workspace_bytes, void* stream) {
-    EMCID_CHECK_ARG(M > 0 && N > 0 && K > 0 && A && B && C && workspace && wgs > 0 && wgs <= 4096);
-    EMCID_CHECK_ARG(aligned16(A) && aligned16(B) && aligned16(workspace) && (lda % 2 == 0) && (ldb % 2 == 0));
-    EMCID_CHECK_ARG(M < (1 << 30) && N < (1 << 30) && K < (1 << 30) && (flags & ~19) == 0);
-    const int tri = flags & 3, lower = (flags >> 4) & 1;
-    EMCID_CHECK_ARG((lower && M == N && tri == 0) || (!lower && (tri == 1 || tri == 2)));
-    EMCID_CHECK_ARG(((M + 127) / 128) * ((N + 127) / 128) <= 16384);      // one ticket counter per 128 x 128 tile
-    if (workspace_bytes < emcid_streamk_workspace_bytes(wgs)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    GemmShape p{A, lda, B, ldb, (int)M, (int)N, (int)K, lower};
-    p.tri = tri;
-    ScopedProf sp(KC_DGEMM, st);
-    const bool launched = tb == 0 ? launch_gemm_f64_streamk2<true, true>(p, EpiAxpby{C, ldc, alpha, 0.0}, st, wgs, (double*)workspace, diag_add)
-                                  : launch_gemm_f64_streamk2<true, false>(p, EpiAxpby{C, ldc, alpha, 0.0}, st, wgs, (double*)workspace, diag_add);
-    if (!launched) return fail(EMCID_ERR_BAD_ARG, __func__, "more 128 x 128 output tiles than ticket counters (16384)");
-    EMCID_CHECK_LAUNCH();
-    return EMCID_OK;
-}
-
-/* diagnostic: later two-phase stream-K launches write 8 shader-clock values per workgroup to stamps_dev (NULL: stop) —
- * [0] start, [1] end, cycles in [2] K loops, [3] partial-tile publishes, [4] last-ticket reductions, [5] epilogues,
- * [6] segments, [7] run index */
 /* diagnostic: chol_step_leaf_kernel writes, per launch slice s < 16 and workgroup b < 512, [start, -, end, kind] (constant
  * 100 MHz clock; kind 1 leaf, 2 trailing tile, 3 shadow tile pair) at stamps_dev[(s * 512 + b) * 4], and the same for the spine
  * launches (kind 4 spine tile, 5 panel tile) at stamps_dev[((16 + s) * 512 + b) * 4]: 32 * 512 * 4 values; null switches it off.
  * Set it before the first edit of the process (captured graphs keep the pointer they were captured with). */
 int emcid_debug_step_stamps(long long* stamps_dev) {
     g_step_stamps = stamps_dev;
-    return EMCID_OK;
-}
-
-int emcid_debug_streamk_stamps(long long* stamps_dev) {
-    g_streamk_stamps = stamps_dev;
-    return EMCID_OK;
-}
-
-int emcid_dgemm_batched_f64(int ta, int tb, int64_t M, int64_t N, int64_t K, double alpha, const double* A, int64_t lda,
-                            int64_t sA, const double* B, int64_t ldb, int64_t sB, double beta, double* C, int64_t ldc, int64_t sC,
-                            int64_t batch, void* stream) {
-    EMCID_CHECK_ARG(M > 0 && N > 0 && K > 0 && A && B && C && batch > 0 && batch <= 65535);
-    EMCID_CHECK_ARG(aligned16(A) && aligned16(B) && (lda % 2 == 0) && (ldb % 2 == 0) && (sA % 2 == 0) && (sB % 2 == 0));
-    EMCID_CHECK_ARG(M < (1 << 30) && N < (1 << 30) && K < (1 << 30) && sA >= 0 && sB >= 0 && sC >= 0);
-    hipStream_t st = (hipStream_t)stream;
-    GemmShape p{A, lda, B, ldb, (int)M, (int)N, (int)K, 0};
-    p.sA = sA; p.sB = sB; p.batch = (int)batch;
-    EpiAxpby e{C, ldc, alpha, beta};
-    e.sC = sC;
-    ScopedProf sp(KC_DGEMM, st);
-    // no K split is asked for here; the launcher's own rule still applies: with beta == 1, small tiles, fewer than 512
-    // workgroups over the whole batch and K >= 256 it splits K (blockIdx.z = batch * ksplit + split) and adds the partials
-    // with f64 atomics.  The per-edit Grams of the UCE closed form call this with beta == 0 and are never split.
-    if (ta == 0 && tb == 0) launch_gemm_f64<true, true>(p, e, st);
-    else if (ta == 0 && tb == 1) launch_gemm_f64<true, false>(p, e, st);
-    else if (ta == 1 && tb == 0) launch_gemm_f64<false, true>(p, e, st);
-    else launch_gemm_f64<false, false>(p, e, st);
-    EMCID_CHECK_LAUNCH();
-    return EMCID_OK;
-}
-
-int emcid_assemble_spd_f64(const float* C, int64_t ldc, const double* Kt64, int64_t Np, int64_t d, int64_t ldk, double lam,
-                           float cw, double* A, int64_t lda, void* stream) {
-    EMCID_CHECK_ARG(C && Kt64 && A && Np > 0 && d > 0);
-    const int64_t dp = round_up(d, NB);
-    EMCID_CHECK_ARG(lda >= dp && ldk >= dp && ldc >= d && (ldk % 2 == 0) && aligned16(Kt64));
-    GemmShape p{Kt64, ldk, Kt64, ldk, (int)dp, (int)dp, (int)Np, 1};
-    {
-        ScopedProf sp(KC_ASSEMBLE, (hipStream_t)stream);
-        launch_gemm_f64<false, false>(p, EpiAssemble{C, ldc, lam, cw, A, lda, (int)d}, (hipStream_t)stream);
-    }
-    EMCID_CHECK_LAUNCH();
     return EMCID_OK;
 }
 
@@ -2084,794 +1323,6 @@ int emcid_cholesky_solve_f64(const double* L, int64_t dp, int64_t lda, const dou
     EMCID_CHECK_ARG(L && invdiag && Bt && Yt && dp > 0 && dp % NB == 0 && Np > 0 && ldb >= dp && lda >= dp);
     EMCID_CHECK_ARG(aligned16(L) && aligned16(Bt) && aligned16(Yt) && lda % 2 == 0 && ldb % 2 == 0);
     return cholesky_solve_impl(L, dp, lda, invdiag, Bt, Yt, Np, ldb, (hipStream_t)stream);
-}
-
-int emcid_delta_w_f64(const double* Rt, int64_t ldr, const double* Xt, int64_t ldx, int64_t Np, int64_t h, int64_t d,
-                      const float* W0, float* W, int64_t ldw, float* dW, double* U, void* stream) {
-    EMCID_CHECK_ARG(Rt && Xt && Np > 0 && h > 0 && d > 0 && ldr % 2 == 0 && ldx % 2 == 0 && aligned16(Rt) && aligned16(Xt));
-    EMCID_CHECK_ARG((W == nullptr) || (W0 != nullptr));
-    GemmShape p{Rt, ldr, Xt, ldx, (int)h, (int)d, (int)Np, 0};
-    {
-        ScopedProf sp(KC_DELTA_W, (hipStream_t)stream);
-        launch_gemm_f64<false, false>(p, EpiDeltaW{W0, W, ldw, dW, d, U, d}, (hipStream_t)stream);
-    }
-    EMCID_CHECK_LAUNCH();
-    return EMCID_OK;
-}
-
-int emcid_axpy_f32(float* W, const float* dW, int64_t n, void* stream) {
-    EMCID_CHECK_ARG(W && dW && n > 0);
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(axpy_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, W, dW, n);
-    EMCID_CHECK_LAUNCH();
-    return EMCID_OK;
-}
-
-int64_t emcid_edit_workspace_bytes(int64_t N, int64_t d, int64_t h) {
-    if (N <= 0 || d <= 0 || h <= 0) return 0;
-    return EditWorkspace(N, d, h).total * (int64_t)sizeof(double);
-}
-
-static int edit_layer_impl(const float* K, const float* Zc, const float* zs_t, const float* C, int64_t N, int64_t d, int64_t h,
-                           double lam, double edit_weight, int layers_left, int64_t n_lo, int64_t n_hi, const float* W0,
-                           float* W, double* Xt_out, double* Rt_out, float* dW_out, double* U_out, void* workspace,
-                           int64_t workspace_bytes, int* info_dev, void* stream) {
-    EMCID_CHECK_ARG(K && Zc && zs_t && C && N > 0 && d > 0 && h > 0 && layers_left > 0 && workspace && info_dev);
-    EMCID_CHECK_ARG(N < (1 << 24) && d <= 32768 && h <= 32768);
-    EMCID_CHECK_ARG(0 <= n_lo && n_lo < n_hi && n_hi <= N);
-    EMCID_CHECK_ARG((W == nullptr) || (W0 != nullptr));
-    EMCID_CHECK_ARG(aligned16(workspace));
-    EditWorkspace ws(N, d, h);
-    if (workspace_bytes < ws.total * (int64_t)sizeof(double))
-        return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small (see emcid_edit_workspace_bytes)");
-    hipStream_t st = (hipStream_t)stream;
-    double* base = (double*)workspace;
-    double *A = base + ws.off_A, *L = base + ws.off_L, *inv = base + ws.off_inv;
-    double *B = base + ws.off_B, *Y = base + ws.off_Y, *R = base + ws.off_R;
-    const double s = sqrt(edit_weight / 0.5);
-    const float cw = (float)(1.0 - edit_weight);  // torch multiplies the fp32 tensor by the scalar rounded to fp32
-    const int64_t rows = n_hi - n_lo;
-
-    {
-        ScopedProf sp(KC_PREP, st);
-        hipLaunchKernelGGL(prep_kr_kernel, dim3((unsigned)ws.Np), dim3(256), 0, st, K, Zc, zs_t, (int)N, (int)d, (int)h, s,
-                           (double)layers_left, B, (int)ws.Np, (int)ws.dp, R, (int)ws.hp);
-    }
-    EMCID_CHECK_LAUNCH();
-    EMCID_TRY(emcid_assemble_spd_f64(C, d, B, ws.Np, d, ws.dp, lam, cw, A, ws.dp, stream));
-    // only this shard's concept rows go through the triangular solves and the dW contraction
-    double* Bs = B + n_lo * ws.dp;
-    EMCID_TRY(factor_and_solve(A, L, ws.dp, ws.dp, inv, info_dev, Bs, Y + n_lo * ws.dp, rows, ws.dp, st));
-    if (W || dW_out || U_out)
-        EMCID_TRY(emcid_delta_w_f64(R + n_lo * ws.hp, ws.hp, Bs, ws.dp, rows, h, d, W0, W, d, dW_out, U_out, stream));
-    if (Xt_out)
-        hipLaunchKernelGGL(copy2d_f64_kernel, dim3((unsigned)rows), dim3(256), 0, st, Bs, ws.dp, Xt_out, d, (int)rows, (int)d);
-    if (Rt_out)
-        hipLaunchKernelGGL(copy2d_f64_kernel, dim3((unsigned)rows), dim3(256), 0, st, R + n_lo * ws.hp, ws.hp, Rt_out, h,
-                           (int)rows, (int)h);
-    EMCID_CHECK_LAUNCH();
-    return EMCID_OK;
-}
-
-int emcid_edit_layer_f64(const float* K, const float* Zc, const float* zs_t, const float* C, int64_t N, int64_t d, int64_t h,
-                         double lam, double edit_weight, int layers_left, const float* W0, float* W, double* Xt_out,
-                         double* Rt_out, float* dW_out, void* workspace, int64_t workspace_bytes, int* info_dev,
-                         void* stream) {
-    return edit_layer_impl(K, Zc, zs_t, C, N, d, h, lam, edit_weight, layers_left, 0, N, W0, W, Xt_out, Rt_out, dW_out,
-                           nullptr, workspace, workspace_bytes, info_dev, stream);
-}
-
-int emcid_edit_layer_shard_f64(const float* K, const float* Zc, const float* zs_t, const float* C, int64_t N, int64_t d,
-                               int64_t h, double lam, double edit_weight, int layers_left, int64_t n_lo, int64_t n_hi,
-                               double* U_partial, double* Xt_out, double* Rt_out, void* workspace, int64_t workspace_bytes,
-                               int* info_dev, void* stream) {
-    EMCID_CHECK_ARG(U_partial != nullptr);
-    return edit_layer_impl(K, Zc, zs_t, C, N, d, h, lam, edit_weight, layers_left, n_lo, n_hi, nullptr, nullptr, Xt_out,
-                           Rt_out, nullptr, U_partial, workspace, workspace_bytes, info_dev, stream);
-}
-
-int emcid_apply_update_f32(const double* U, const float* W0, float* W, float* dW, int64_t n, void* stream) {
-    EMCID_CHECK_ARG(U && n > 0 && (W || dW) && ((W == nullptr) || (W0 != nullptr)));
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(apply_u_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, U, W0, W, dW, n);
-    EMCID_CHECK_LAUNCH();
-    return EMCID_OK;
-}
-
-/* ---- dual (Woodbury) solver ------------------------------------------------------------------------------------- */
-
-int64_t emcid_cov_factor_workspace_bytes(int64_t n_layers, int64_t d) {
-    if (n_layers <= 0 || d <= 0) return 0;
-    const int64_t dp = round_up(d, NB);
-    return n_layers * (3 * dp * dp + inv_doubles(dp)) * (int64_t)sizeof(double);
-}
-
-int emcid_factor_cov_f64(const float* const* C_host_list, int64_t n_layers, int64_t d, double lam, double edit_weight,
-                         void* workspace, int64_t workspace_bytes, int* info_dev, void* stream) {
-    EMCID_CHECK_ARG(C_host_list && n_layers > 0 && n_layers <= 32 && d > 0 && d <= 32768 && workspace && info_dev);
-    EMCID_CHECK_ARG(aligned16(workspace));
-    if (workspace_bytes < emcid_cov_factor_workspace_bytes(n_layers, d))
-        return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small (see emcid_cov_factor_workspace_bytes)");
-    const int64_t dp = round_up(d, NB), s_mat = dp * dp, s_inv = inv_doubles(dp);
-    double* Mb = (double*)workspace;                 // [n_layers][dp*dp]  lam*C' (consumed by the factorization)
-    double* Lb = Mb + n_layers * s_mat;              // [n_layers][dp*dp]  factors
-    double* Ib = Lb + n_layers * s_mat;              // [n_layers][inv_doubles]
-    // [n_layers][dp*dp] after Ib: X = inv(L), explicit, built per layer by emcid_cov_inverse_f64
-    CovPtrs cp;
-    for (int i = 0; i < 32; ++i) cp.c[i] = i < n_layers ? C_host_list[i] : nullptr;
-    for (int i = 0; i < n_layers; ++i) EMCID_CHECK_ARG(cp.c[i] != nullptr);
-    const float cw = (float)(1.0 - edit_weight);
-    hipStream_t st = (hipStream_t)stream;
-    GraphKey key = make_key(2, {Mb, info_dev}, {n_layers, d, 0, 0, 0});
-    memcpy(&key.num[2], &lam, sizeof(double));
-    memcpy(&key.num[3], &cw, sizeof(float));
-    for (int i = 0; i < n_layers; ++i)   // every C pointer takes part in the key (6 slots, then folded)
-        if (i < 6) key.ptr[2 + i] = cp.c[i]; else key.num[4] = key.num[4] * 1000003 + (int64_t)(uintptr_t)cp.c[i];
-    return with_graph(key, st, [&](hipStream_t s) {
-        hipLaunchKernelGGL(scale_cov_kernel, dim3((unsigned)dp, (unsigned)n_layers), dim3(256), 0, s, cp, (int)d, (int)dp, lam, cw,
-                           Mb, s_mat);
-        return cholesky_serial(Mb, Lb, dp, dp, Ib, info_dev, s, (int)n_layers, s_mat, s_inv);
-    });
-}
-
-/* X_l = inv(L_l) for ONE layer of a factored workspace (needs emcid_factor_cov_f64 earlier on the same stream, or an
- * event dependency on it).  Per layer so that the first edited layer's solve can start while the later layers' inverse
- * factors are still being built underneath it. */
-int emcid_cov_inverse_f64(void* cov_factor_ws, int64_t n_layers, int64_t d, int64_t first_layer, int64_t count, void* stream) {
-    EMCID_CHECK_ARG(cov_factor_ws && n_layers > 0 && n_layers <= 32 && d > 0 && d <= 32768 && aligned16(cov_factor_ws));
-    EMCID_CHECK_ARG(0 <= first_layer && count > 0 && first_layer + count <= n_layers);
-    const int64_t dp = round_up(d, NB), s_mat = dp * dp, s_inv = inv_doubles(dp);
-    double* Mb = (double*)cov_factor_ws + first_layer * s_mat;          // consumed by the factorization: scratch now
-    const double* Lb = (const double*)cov_factor_ws + (n_layers + first_layer) * s_mat;
-    const double* Ib = (const double*)cov_factor_ws + 2 * n_layers * s_mat + first_layer * s_inv;
-    double* Xb = (double*)cov_factor_ws + n_layers * (2 * s_mat + s_inv) + first_layer * s_mat;
-    return with_graph(make_key(7, {Mb, Lb, Ib, Xb}, {dp, count}), (hipStream_t)stream, [&](hipStream_t s) {
-        return build_full_inverse(Lb, dp, dp, Ib, Xb, Mb, (int)count, s_mat, s_inv, s);   // batched over the range
-    });
-}
-
-/* ---- a factored workspace at another scale: chol(a M) = sqrt(a) chol(M) ---------------------------------------------------
- * One launch over the three factor regions of every layer: the NB x NB tiles of L on and below the diagonal times sqrt(a), the
- * same tiles of X = inv(L) and the whole block of diagonal-block inverses times 1/sqrt(a).  (A diagonal tile is copied whole:
- * whatever the factorization left above the diagonal inside it travels along, scaled.)  Nothing above the block diagonal is
- * read or written, and the consumed M region is left alone.  Every access is a double2 (128 bits): dp is a multiple of 128 and
- * every region starts on an even number of doubles from the 16-byte aligned base.  src == dst scales in place. */
-__global__ __launch_bounds__(256) void cov_factor_rescale_kernel(const double* src, double* dst, int64_t off_L, int64_t off_I,
-                                                                 int64_t off_X, int64_t s_mat, int64_t s_inv, int dp, int n_tri,
-                                                                 double gain_L, double gain_inv, int with_inverse) {
-    const int64_t layer = blockIdx.y;
-    const int region = blockIdx.z;            // 0: L, 1: the diagonal-block inverses, 2: X
-    if (region == 1) {
-        const double2* s = reinterpret_cast<const double2*>(src + off_I + layer * s_inv);
-        double2* o = reinterpret_cast<double2*>(dst + off_I + layer * s_inv);
-        for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < s_inv / 2; i += (int64_t)gridDim.x * 256) {
-            double2 v = s[i];
-            v.x *= gain_inv;
-            v.y *= gain_inv;
-            o[i] = v;
-        }
-        return;
-    }
-    if (region == 2 && !with_inverse) return;
-    const int t = blockIdx.x;                 // tile (I, J), J <= I, of the block lower triangle: t = I (I + 1) / 2 + J
-    if (t >= n_tri) return;
-    int I = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-    while ((I + 1) * (I + 2) / 2 <= t) ++I;
-    while (I * (I + 1) / 2 > t) --I;
-    const int J = t - I * (I + 1) / 2;
-    const int64_t base = (region == 0 ? off_L : off_X) + layer * s_mat + (int64_t)I * NB * dp + (int64_t)J * NB;
-    const double g = region == 0 ? gain_L : gain_inv;
-    // 128 rows of 64 double2: a wavefront covers one row's 1 KiB
-    for (int e = threadIdx.x; e < NB * (NB / 2); e += 256) {
-        const int r = e / (NB / 2), c2 = e % (NB / 2);
-        const int64_t at = base + (int64_t)r * dp + 2 * c2;
-        double2 v = *reinterpret_cast<const double2*>(src + at);
-        v.x *= g;
-        v.y *= g;
-        *reinterpret_cast<double2*>(dst + at) = v;
-    }
-}
-
-int emcid_cov_factor_rescale_f64(const void* src_ws, void* dst_ws, int64_t workspace_bytes, int64_t n_layers, int64_t d, double a,
-                                 int with_inverse, void* stream) {
-    EMCID_CHECK_ARG(src_ws && dst_ws && n_layers > 0 && n_layers <= 32 && d > 0 && d <= 32768);
-    EMCID_CHECK_ARG(aligned16(src_ws) && aligned16(dst_ws) && a > 0.0 && a < 1e300);
-    if (workspace_bytes < emcid_cov_factor_workspace_bytes(n_layers, d))
-        return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small (see emcid_cov_factor_workspace_bytes)");
-    const int64_t dp = round_up(d, NB), s_mat = dp * dp, s_inv = inv_doubles(dp), nt = dp / NB;
-    EMCID_CHECK_ARG(s_inv % 2 == 0);
-    const int n_tri = (int)(nt * (nt + 1) / 2);
-    const double root = sqrt(a);
-    // grid: x = the tiles of the block lower triangle, y = layer, z = region.  Regions 0 and 2 take one tile per workgroup (all of
-    // region 2 leave at once without with_inverse); region 1, the small block of diagonal-block inverses, walks its s_inv / 2
-    // double2 with the same n_tri workgroups as a grid-stride loop: one launch for the three regions.
-    hipLaunchKernelGGL(cov_factor_rescale_kernel, dim3((unsigned)n_tri, (unsigned)n_layers, 3), dim3(256), 0, (hipStream_t)stream,
-                       (const double*)src_ws, (double*)dst_ws, n_layers * s_mat, 2 * n_layers * s_mat, n_layers * (2 * s_mat + s_inv),
-                       s_mat, s_inv, (int)dp, n_tri, root, 1.0 / root, with_inverse);
-    EMCID_CHECK_LAUNCH();
-    return EMCID_OK;
-}
-
-/* ---- fold a preserved key set into the base factor (edit sessions) -------------------------------------------------------------
- * A session whose preserved set is full takes its M rows into a factor of its own: with P the stacked (scaled) keys,
- *     A' = A0 + P^T P,   P = Yp L_s^T,   L_s = sqrt(lam_ratio) L_src   (Yp = P L_s^-T is what the steps kept),
- * and A' is factored like lam C' itself, so every dual stage runs on it unchanged with M = 0.  `base` carries A0 (and every
- * earlier fold's P^T P) in fp64 between folds: the SYRK accumulates into it, the factorization consumes a copy.
- * Both kernels walk the NB x NB tiles on and below the block diagonal, one tile per workgroup, 128 bits per access. */
-__device__ __forceinline__ void lower_tile_of(int t, int& I, int& J) {      // t = I (I + 1) / 2 + J, J <= I
-    I = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-    while ((I + 1) * (I + 2) / 2 <= t) ++I;
-    while (I * (I + 1) / 2 > t) --I;
-    J = t - I * (I + 1) / 2;
-}
-
-// base = lam * double(fl32(fl32(C * cw) / 0.5f)) inside [0, d)^2, identity on the padding: scale_cov_kernel's values for one layer
-// (the diagonal tiles are filled whole: the SYRK that follows reads and writes whole tiles)
-__global__ __launch_bounds__(256) void fold_base_fill_kernel(const float* __restrict__ C, int d, int dp, double lam, float cw,
-                                                             double* __restrict__ base) {
-    int I, J;
-    lower_tile_of((int)blockIdx.x, I, J);
-    for (int e = threadIdx.x; e < NB * (NB / 2); e += 256) {
-        const int i = I * NB + e / (NB / 2), j = J * NB + 2 * (e % (NB / 2));
-        double2 v;
-        if (i < d) {
-            const float* row = C + (int64_t)i * d;
-            const float c0 = j < d ? row[j] * cw : 0.0f, c1 = j + 1 < d ? row[j + 1] * cw : 0.0f;
-            v.x = j < d ? lam * (double)(c0 / 0.5f) : 0.0;
-            v.y = j + 1 < d ? lam * (double)(c1 / 0.5f) : 0.0;
-        } else {
-            v.x = i == j ? 1.0 : 0.0;
-            v.y = i == j + 1 ? 1.0 : 0.0;
-        }
-        *reinterpret_cast<double2*>(base + (int64_t)i * dp + j) = v;
-    }
-}
-
-// dst = gain * src on the same tiles; lower_only: zeros above the diagonal inside the diagonal tiles (a factor as the
-// factorization leaves it holds no defined values there, and a triangular GEMM hint skips K tiles, not elements)
-__global__ __launch_bounds__(256) void fold_copy_lower_kernel(const double* __restrict__ src, double* __restrict__ dst, int dp,
-                                                              double gain, int lower_only) {
-    int I, J;
-    lower_tile_of((int)blockIdx.x, I, J);
-    for (int e = threadIdx.x; e < NB * (NB / 2); e += 256) {
-        const int i = I * NB + e / (NB / 2), j = J * NB + 2 * (e % (NB / 2));
-        const int64_t at = (int64_t)i * dp + j;
-        double2 v = *reinterpret_cast<const double2*>(src + at);
-        v.x = (lower_only && j > i) ? 0.0 : v.x * gain;
-        v.y = (lower_only && j + 1 > i) ? 0.0 : v.y * gain;
-        *reinterpret_cast<double2*>(dst + at) = v;
-    }
-}
-
-int64_t emcid_cov_factor_fold_workspace_bytes(int64_t M, int64_t d) {
-    if (M <= 0 || d <= 0) return 0;
-    return M * round_up(d, NB) * (int64_t)sizeof(double);          // Q = Yp L_s^T [M, dp]
-}
-
-int emcid_cov_factor_fold_f64(const void* src_ws, double lam_ratio, const double* Yp, int64_t ldy, int64_t M, int64_t capacity,
-                              const float* C, double lam, double edit_weight, int fill_base, void* dst_ws, int64_t n_layers,
-                              int64_t d, int64_t layer_index, double* base, void* workspace, int64_t workspace_bytes,
-                              int* info_dev, void* stream) {
-    EMCID_CHECK_ARG(src_ws && dst_ws && Yp && base && workspace && info_dev && n_layers > 0 && n_layers <= 32 && d > 0 && d <= 32768);
-    EMCID_CHECK_ARG(0 <= layer_index && layer_index < n_layers);
-    EMCID_CHECK_ARG(M > 0 && M <= capacity && capacity < (int64_t)1 << 30);
-    EMCID_CHECK_ARG(lam_ratio > 0.0 && lam_ratio < 1e300);
-    EMCID_CHECK_ARG(src_ws != dst_ws || lam_ratio == 1.0);      // in place: the caller's own workspace, at the caller's own lam
-    EMCID_CHECK_ARG(!fill_base || (C && lam > 0.0 && lam < 1e300 && edit_weight >= 0.0 && edit_weight <= 1.0));
-    const int64_t dp = round_up(d, NB), s_mat = dp * dp, s_inv = inv_doubles(dp), nt = dp / NB;
-    EMCID_CHECK_ARG(aligned16(src_ws) && aligned16(dst_ws) && aligned16(Yp) && aligned16(base) && aligned16(workspace));
-    EMCID_CHECK_ARG(ldy >= dp && ldy % 2 == 0);
-    if (workspace_bytes < emcid_cov_factor_fold_workspace_bytes(M, d))
-        return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small (see emcid_cov_factor_fold_workspace_bytes)");
-    hipStream_t st = (hipStream_t)stream;
-    const double* Lsrc = (const double*)src_ws + (n_layers + layer_index) * s_mat;
-    double* Mb = (double*)dst_ws + layer_index * s_mat;                 // consumed by the factorization; scratch before and after
-    double* Lb = (double*)dst_ws + (n_layers + layer_index) * s_mat;
-    double* Ib = (double*)dst_ws + 2 * n_layers * s_mat + layer_index * s_inv;
-    double* Xb = (double*)dst_ws + n_layers * (2 * s_mat + s_inv) + layer_index * s_mat;
-    double* Q = (double*)workspace;
-    const unsigned n_tri = (unsigned)(nt * (nt + 1) / 2);
-    // the keys back from factor coordinates: Q = Yp L_s^T against a clean lower-triangular copy of L_s in the M region
-    hipLaunchKernelGGL(fold_copy_lower_kernel, dim3(n_tri), dim3(256), 0, st, Lsrc, Mb, (int)dp, sqrt(lam_ratio), 1);
-    {
-        ScopedProf sp(KC_INV_APPLY, st);
-        GemmShape g{Yp, ldy, Mb, dp, (int)M, (int)dp, (int)dp, 0};
-        g.tri = 1;       // B(k, n) = L_s[n][k], zero for k > n
-        g.pair = 1;
-        launch_gemm_f64<true, true>(g, EpiAxpby{Q, dp, 1.0, 0.0}, st, 2);
-    }
-    if (fill_base)
-        hipLaunchKernelGGL(fold_base_fill_kernel, dim3(n_tri), dim3(256), 0, st, C, (int)d, (int)dp, lam, (float)(1.0 - edit_weight),
-                           base);
-    {
-        ScopedProf sp(KC_ASSEMBLE, st);      // base += Q^T Q on the lower tiles: both operands stored [K = M][dp]
-        GemmShape g{Q, dp, Q, dp, (int)dp, (int)dp, (int)M, 1};
-        launch_gemm_f64<false, false>(g, EpiAxpby{base, dp, 1.0, 1.0}, st);
-    }
-    hipLaunchKernelGGL(fold_copy_lower_kernel, dim3(n_tri), dim3(256), 0, st, base, Mb, (int)dp, 1.0, 0);
-    EMCID_TRY(cholesky_serial(Mb, Lb, dp, dp, Ib, info_dev, st, 1, s_mat, s_inv));
-    EMCID_TRY(build_full_inverse(Lb, dp, dp, Ib, Xb, Mb, 1, s_mat, s_inv, st));
-    EMCID_CHECK_LAUNCH();
-    return EMCID_OK;
-}
-
-int64_t emcid_edit_dual_workspace_bytes(int64_t N, int64_t d, int64_t h) {
-    if (N <= 0 || d <= 0 || h <= 0) return 0;
-    return DualWorkspace(N, d, h).total * (int64_t)sizeof(double);
-}
-
-/* stage 1: Kt64 = s*K, Rt, and the shard's rows of Pt = Kt64 M^-1 (into Pt_rows_out if given, else only the workspace) */
-int emcid_edit_dual_stage1_f64(const float* K, const float* Zc, const float* zs_t, int64_t N, int64_t d, int64_t h,
-                               double edit_weight, int layers_left, double lam_ratio, const void* cov_factor_ws, int64_t n_layers,
-                               int64_t layer_index, int64_t n_lo, int64_t n_hi, int use_inverse, void* workspace,
-                               int64_t workspace_bytes, void* stream) {
-    EMCID_CHECK_ARG(K && Zc && zs_t && N > 0 && d > 0 && h > 0 && layers_left > 0 && cov_factor_ws && workspace);
-    EMCID_CHECK_ARG(0 <= layer_index && layer_index < n_layers && 0 <= n_lo && n_lo < n_hi && n_hi <= N);
-    EMCID_CHECK_ARG(lam_ratio > 0.0 && lam_ratio < 1e300);
-    DualWorkspace ws(N, d, h);
-    if (workspace_bytes < ws.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    double* base = (double*)workspace;
-    double *Kt = base + ws.off_K, *Pt = base + ws.off_P, *Y = base + ws.off_Y, *R = base + ws.off_R;
-    const int64_t dp = ws.dp, s_mat = dp * dp;
-    const double* Lb = (const double*)cov_factor_ws + n_layers * s_mat + layer_index * s_mat;
-    const double* Ib = (const double*)cov_factor_ws + 2 * n_layers * s_mat + layer_index * inv_doubles(dp);
-    const double s = sqrt(edit_weight / 0.5);
-    {
-        ScopedProf sp(KC_PREP, st);
-        hipLaunchKernelGGL(prep_kr_kernel, dim3((unsigned)ws.Np), dim3(256), 0, st, K, Zc, zs_t, (int)N, (int)d, (int)h, s,
-                           (double)layers_left, Kt, (int)ws.Np, (int)dp, R, (int)ws.hp, 1.0 / sqrt(lam_ratio));
-    }
-    const int64_t rows = n_hi - n_lo;
-    if (use_inverse) {
-        // Pt = (Kt X^T) X : both triangular solves against M = L L^T are GEMMs against the explicit X = inv(L)
-        const double* Xb = cov_inverse(cov_factor_ws, n_layers, dp, layer_index);
-        apply_inverse_forward(Xb, dp, Kt + n_lo * dp, Y + n_lo * dp, (int)rows, st, base + ws.off_SK);
-        apply_inverse_backward(Xb, dp, Y + n_lo * dp, (int)rows, (int)dp, Pt + n_lo * dp, dp, st, base + ws.off_SK);
-        EMCID_CHECK_LAUNCH();
-        return EMCID_OK;
-    }
-    if (hipMemcpyAsync(Pt + n_lo * dp, Kt + n_lo * dp, rows * dp * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return fail(EMCID_ERR_HIP, __func__, "hipMemcpyAsync");
-    return with_graph(make_key(3, {Lb, Ib, Pt + n_lo * dp, Y + n_lo * dp}, {dp, rows}), st, [&](hipStream_t q) {
-        return cholesky_solve_impl(Lb, dp, dp, Ib, Pt + n_lo * dp, Y + n_lo * dp, rows, dp, q);
-    });
-}
-
-/* pointer to the Pt stack [Np, dp] inside a dual workspace (multi-GPU: ranks all-gather their row blocks in place) */
-double* emcid_edit_dual_pt(void* workspace, int64_t N, int64_t d, int64_t h) {
-    if (!workspace || N <= 0 || d <= 0 || h <= 0) return nullptr;
-    return (double*)workspace + DualWorkspace(N, d, h).off_P;
-}
-
-/* stage 2 (needs ALL rows of Pt): S = I + Pt Kt^T, S = L_S L_S^T, adj_k = (S^-1 Pt)^T  [d, Np], U = Rt^T Xt, W = W0 + float(U) */
-int emcid_edit_dual_stage2_f64(int64_t N, int64_t d, int64_t h, double lam_ratio, const float* W0, float* W, double* adjk_out, double* Rt_out,
-                               float* dW_out, void* workspace, int64_t workspace_bytes, int* info_dev, void* stream) {
-    EMCID_CHECK_ARG(N > 0 && d > 0 && h > 0 && workspace && info_dev && ((W == nullptr) || (W0 != nullptr)));
-    EMCID_CHECK_ARG(lam_ratio > 0.0 && lam_ratio < 1e300);
-    DualWorkspace ws(N, d, h);
-    if (workspace_bytes < ws.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    double* base = (double*)workspace;
-    double *Kt = base + ws.off_K, *Pt = base + ws.off_P, *R = base + ws.off_R, *S = base + ws.off_S, *LS = base + ws.off_LS;
-    double *invS = base + ws.off_invS, *PT = base + ws.off_PT, *Y2 = base + ws.off_Y2;
-    const int64_t dp = ws.dp, Np = ws.Np;
-    EMCID_TRY(with_graph(make_key(4, {Kt, Pt, S, LS, invS, PT, Y2, info_dev}, {dp, Np, N}), st, [&](hipStream_t q) {
-        if (Np > N)   // rows of the padding concepts: zero (their Kt rows are zero, so S gets identity rows there)
-            hipLaunchKernelGGL(zero_f64_kernel, dim3(256), dim3(256), 0, q, Pt + N * dp, (Np - N) * dp);
-        assemble_dual_system(Pt, Kt, dp, S, (int)Np, q, base + ws.off_SK);
-        EMCID_TRY(cholesky_impl(S, LS, Np, Np, invS, info_dev, q));
-        hipLaunchKernelGGL(transpose_f64_kernel, dim3((unsigned)(dp / 32), (unsigned)(Np / 32)), dim3(256), 0, q, Pt, dp, PT, Np,
-                           (int)Np, (int)dp);
-        return cholesky_solve_impl(LS, Np, Np, invS, PT, Y2, dp, Np, q);   // PT := PT S^-1  ->  adj_k padded [dp, Np]
-    }));
-    if (W || dW_out) {
-        ScopedProf sp(KC_DELTA_W, st);
-        GemmShape g{R, ws.hp, PT, Np, (int)h, (int)d, (int)Np, 0};
-        launch_gemm_f64<false, true>(g, EpiDeltaW{W0, W, d, dW_out, d, nullptr, d}, st);
-    }
-    // the workspace holds sqrt(lam_ratio) * adj_k and Rt / sqrt(lam_ratio) (stage 1's gain): the caller gets both in its own scale
-    const double root = sqrt(lam_ratio);
-    if (adjk_out)
-        hipLaunchKernelGGL(copy2d_f64_kernel, dim3((unsigned)d), dim3(256), 0, st, PT, Np, adjk_out, N, (int)d, (int)N, 1.0 / root);
-    if (Rt_out) hipLaunchKernelGGL(copy2d_f64_kernel, dim3((unsigned)N), dim3(256), 0, st, R, ws.hp, Rt_out, h, (int)N, (int)h, root);
-    EMCID_CHECK_LAUNCH();
-    return EMCID_OK;
-}
-
-/* ---- dual solver, apply-only form: adj_k is never formed -----------------------------------------------------------
- * With M = L L^T:  Yt = Kt64 L^-T,  S = I + Yt Yt^T,  Z = S^-1 Rt,  U = Rt^T Xt = (Z^T Yt) L^-1,  W = W0 + float(U).
- * One forward solve on the N concept rows, a true SYRK, the N x N Cholesky, two solves with only h right-hand sides,
- * one GEMM and one backward solve on h rows.  Same algebra as stage1 + stage2 by associativity. */
-int emcid_edit_dual_apply_stage1_f64(const float* K, const float* Zc, const float* zs_t, int64_t N, int64_t d, int64_t h,
-                                     double edit_weight, int layers_left, double lam_ratio, const void* cov_factor_ws, int64_t n_layers,
-                                     int64_t layer_index, int64_t n_lo, int64_t n_hi, int use_inverse, void* workspace,
-                                     int64_t workspace_bytes, void* stream) {
-    EMCID_CHECK_ARG(K && Zc && zs_t && N > 0 && d > 0 && h > 0 && layers_left > 0 && cov_factor_ws && workspace);
-    EMCID_CHECK_ARG(0 <= layer_index && layer_index < n_layers && 0 <= n_lo && n_lo < n_hi && n_hi <= N);
-    EMCID_CHECK_ARG(lam_ratio > 0.0 && lam_ratio < 1e300);
-    DualWorkspace ws(N, d, h);
-    if (workspace_bytes < ws.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    double* base = (double*)workspace;
-    double *Kt = base + ws.off_K, *Bs = base + ws.off_P, *Yt = base + ws.off_Y, *R = base + ws.off_R;
-    const int64_t dp = ws.dp, s_mat = dp * dp;
-    const double* Lb = (const double*)cov_factor_ws + n_layers * s_mat + layer_index * s_mat;
-    const double* Ib = (const double*)cov_factor_ws + 2 * n_layers * s_mat + layer_index * inv_doubles(dp);
-    const double s = sqrt(edit_weight / 0.5);
-    {
-        ScopedProf sp(KC_PREP, st);
-        hipLaunchKernelGGL(prep_kr_kernel, dim3((unsigned)ws.Np), dim3(256), 0, st, K, Zc, zs_t, (int)N, (int)d, (int)h, s,
-                           (double)layers_left, Kt, (int)ws.Np, (int)dp, R, (int)ws.hp, 1.0 / sqrt(lam_ratio));
-    }
-    const int64_t rows = n_hi - n_lo;
-    if (use_inverse) {
-        // the whole concept range: run over the Np padded rows (Kt's padding rows are zero, so are the products) — every
-        // 128-row tile then lies inside the operand and takes the interior fast path of the stream-K K loop
-        const int64_t gemm_rows = (n_lo == 0 && n_hi == N) ? ws.Np : rows;
-        apply_inverse_forward(cov_inverse(cov_factor_ws, n_layers, dp, layer_index), dp, Kt + n_lo * dp, Yt + n_lo * dp, (int)gemm_rows,
-                              st, base + ws.off_SK);
-        // stage 1 leaves the padding rows [N, Np) of Yt zero (the later stages rely on it): the full-range GEMM has just produced
-        // them; a partial range (row-sharded callers) zeroes them here
-        if (gemm_rows != ws.Np && ws.Np > N)
-            hipLaunchKernelGGL(zero_f64_kernel, dim3(256), dim3(256), 0, st, Yt + N * dp, (ws.Np - N) * dp);
-        EMCID_CHECK_LAUNCH();
-        return EMCID_OK;
-    }
-    if (ws.Np > N) hipLaunchKernelGGL(zero_f64_kernel, dim3(256), dim3(256), 0, st, Yt + N * dp, (ws.Np - N) * dp);
-    if (hipMemcpyAsync(Bs + n_lo * dp, Kt + n_lo * dp, rows * dp * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess)
-        return fail(EMCID_ERR_HIP, __func__, "hipMemcpyAsync");
-    return with_graph(make_key(5, {Lb, Ib, Bs + n_lo * dp, Yt + n_lo * dp}, {dp, rows}), st, [&](hipStream_t q) {
-        trsm_forward(Lb, dp, dp, Ib, Bs + n_lo * dp, Yt + n_lo * dp, (int)rows, dp, q);
-        return check_launch("emcid_edit_dual_apply_stage1_f64");
-    });
-}
-
-/* address of the Yt stack [Np, dp] inside a dual workspace (multi-GPU: ranks all-gather their row blocks there) */
-double* emcid_edit_dual_yt(void* workspace, int64_t N, int64_t d, int64_t h) {
-    if (!workspace || N <= 0 || d <= 0 || h <= 0) return nullptr;
-    return (double*)workspace + DualWorkspace(N, d, h).off_Y;
-}
-
-/* The first part of stage 2 on its own: S = I + Yt Yt^T.  A caller that wants to start other work exactly when the
- * latency-bound Cholesky of S begins (the engine builds the next layer's inverse factor on a second stream then) calls
- * this, records its event, and passes assembled = 1 to stage 2. */
-int emcid_edit_dual_apply_assemble_f64(int64_t N, int64_t d, int64_t h, void* workspace, int64_t workspace_bytes, void* stream) {
-    EMCID_CHECK_ARG(N > 0 && d > 0 && h > 0 && workspace);
-    DualWorkspace ws(N, d, h);
-    if (workspace_bytes < ws.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    double* base = (double*)workspace;
-    double *Yt = base + ws.off_Y, *S = base + ws.off_S;
-    const int64_t dp = ws.dp, Np = ws.Np;
-    assemble_dual_system(Yt, Yt, dp, S, (int)Np, st, base + ws.off_SK);
-    EMCID_CHECK_LAUNCH();
-    return EMCID_OK;
-}
-
-int emcid_edit_dual_apply_stage2_f64(int64_t N, int64_t d, int64_t h, const void* cov_factor_ws, int64_t n_layers,
-                                     int64_t layer_index, int use_inverse, int assembled, const float* W0, float* W,
-                                     float* dW_out, void* workspace, int64_t workspace_bytes, int* info_dev, void* stream) {
-    EMCID_CHECK_ARG(N > 0 && d > 0 && h > 0 && workspace && info_dev && cov_factor_ws && ((W == nullptr) || (W0 != nullptr)));
-    EMCID_CHECK_ARG(0 <= layer_index && layer_index < n_layers && (W || dW_out));
-    DualWorkspace ws(N, d, h);
-    if (workspace_bytes < ws.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    double* base = (double*)workspace;
-    double *Yt = base + ws.off_Y, *R = base + ws.off_R, *S = base + ws.off_S, *LS = base + ws.off_LS, *invS = base + ws.off_invS;
-    double *RT = base + ws.off_PT, *Y2 = base + ws.off_Y2, *V = base + ws.off_V, *U = base + ws.off_U;
-    const int64_t dp = ws.dp, Np = ws.Np, hp = ws.hp, s_mat = dp * dp;
-    const double* Lb = (const double*)cov_factor_ws + n_layers * s_mat + layer_index * s_mat;
-    const double* Ib = (const double*)cov_factor_ws + 2 * n_layers * s_mat + layer_index * inv_doubles(dp);
-    // P = Yt X rides in the Cholesky's leaf launches (ShadowJob) when X is explicit and the fused schedule runs: then
-    // U = Z^T P is one GEMM and the GEMM against the triangle after the N x N solve (U = (Z^T Yt) X) disappears from the chain
-    static const int shadow_env = env_flag("EMCID_SHADOW_P", 1);      // 0: never, 1: when it fits under the leaves, 2: always
-    bool shadow = shadow_env && use_inverse && cholesky_takes_shadow(Np);
-    if (shadow && shadow_env == 1) {
-        // The product only pays while a launch's shadow tiles finish about when its leaf does (~36 us).  Measured on MI355X
-        // (scripts/step_stamps.py): a tile pair's slice costs ~9 us + 1.5 us per 16-deep K step, one workgroup per compute unit.
-        // SD dims, N = 1000: 25 steps, 192 workgroups -> 46 us; SDXL TE2 (d = 5120) at N = 1000: 41 steps in two rounds -> no.
-        const int64_t ntl = (dp + SH_BN - 1) / SH_BN, nb = Np / NB;
-        const int64_t steps = ((ntl + 1) * (SH_BN / 16) + nb - 1) / nb;
-        const int64_t wgs = ((Np + SH_BM - 1) / SH_BM) * ((ntl + 1) / 2), rounds = (wgs + 239) / 240;
-        shadow = rounds * (9.0 + 1.5 * (double)steps) <= 50.0;
-    }
-    double* P = base + ws.off_P;
-    const double* X = use_inverse ? cov_inverse(cov_factor_ws, n_layers, dp, layer_index) : nullptr;
-    // Few concepts (a 100-concept edit: Np = 128, no chain of leaves to ride in): U = Z^T (Yt X) with the triangle multiplied on the
-    // Np-row side as a launch of its own, instead of U = (Z^T Yt) X on the h-row side — 128 rows against 768 at SD dims
-    // (61 + ~15 us instead of ~20 + 155 per layer).  EMCID_P_FIRST=0: the h-side form.
-    const bool p_first = !shadow && use_inverse && Np < h;
-    const bool xrow = cholesky_takes_shadow(Np);       // (= the fused leaf / spine schedule runs)
-    double *XT = base + ws.off_XT, *TT = base + ws.off_TT;
-    EMCID_TRY(with_graph(make_key(6, {Yt, R, S, LS, RT, V, U, info_dev},
-                                  {dp, Np, N, hp, (int64_t)(uintptr_t)Lb,
-                                   use_inverse + 2 * (assembled != 0) + 4 * (int)shadow + 8 * h + ((int64_t)p_first << 31) + ((int64_t)xrow << 30) + (d << 32)}),
-                         st,
-                         [&](hipStream_t q) {
-        if (!assembled) {
-            assemble_dual_system(Yt, Yt, dp, S, (int)Np, q, base + ws.off_SK);      // S = I + Yt Yt^T (lower tiles)
-        }
-        if (p_first) apply_inverse_backward(X, dp, Yt, (int)Np, (int)dp, P, dp, q, base + ws.off_SK);       // P = Yt X
-        ShadowJob job{Yt, dp, X, dp, P, dp, (int)Np, (int)dp, (int)dp, 0, nullptr, 0, 0, 0};
-        job.wgs = (int)((Np + SH_BM - 1) / SH_BM) * (int)(((dp + SH_BN - 1) / SH_BN + 1) / 2);
-        // XS = inv(LS) rides in the factorization's launches (XrowJob), transposed
-        const XrowJob xj{XT, Np, TT};
-        EMCID_TRY(cholesky_impl(S, LS, Np, Np, invS, info_dev, q, shadow ? &job : nullptr, xrow ? &xj : nullptr));
-        // RT[h, Np] = Rt^T ; Z^T = RT S^-1 (two solves with h rows)
-        EMCID_TRY(solve_schur_rhs(R, hp, h, Np, LS, invS, xrow ? XT : nullptr, S, RT, Y2, q));
-        if (!shadow && !p_first) {
-            ScopedProf sp(KC_DELTA_W, q);       // V[h, dp] = Z^T Yt
-            GemmShape g{RT, Np, Yt, dp, (int)h, (int)dp, (int)Np, 0};
-            launch_gemm_f64<true, false>(g, EpiAxpby{V, dp, 1.0, 0.0}, q);
-        }
-        if (!use_inverse) trsm_backward(Lb, dp, dp, Ib, V, U, (int)h, dp, q);   // U L = V by block substitution
-        return check_launch("emcid_edit_dual_apply_stage2_f64");
-    }));
-    if (shadow || p_first) {
-        // U = Z^T P straight into the weights: W = W0 + float(U), dW = float(U) in the GEMM's epilogue (outside the cached graph:
-        // W0 / W / dW are the caller's tensors and change from layer to layer and call to call)
-        ScopedProf sp(KC_DELTA_W, st);
-        GemmShape g{RT, Np, P, dp, (int)h, (int)d, (int)Np, 0};
-        launch_gemm_f64<true, false>(g, EpiDeltaW{W0, W, d, dW_out, d, nullptr, 0}, st, -1);      // the launcher's choice: 32 x 64 tiles
-        EMCID_CHECK_LAUNCH();
-        return EMCID_OK;
-    }
-    if (use_inverse)   // U = V inv(L)  (V's padding columns are zero: Kt's are, X is the identity there)
-        apply_inverse_backward(X, dp, V, (int)h, (int)dp, U, dp, st, base + ws.off_SK);
-    hipLaunchKernelGGL(apply_u2d_kernel, dim3((unsigned)h), dim3(256), 0, st, U, dp, W0, W, dW_out, (int)d);
-    EMCID_CHECK_LAUNCH();
-    return EMCID_OK;
-}
-
-/* ---- dual solver, apply-only form, with a PRESERVED key set (edit sessions) ------------------------------------------------
- * The keys of earlier steps enter the preserved second moment: A = lam C' + P^T P + Kt^T Kt, P the stacked earlier Kt.  In factor
- * coordinates (Yp = P X^T, rows kept verbatim, Lp = chol(I + Yp Yp^T)) a step with N new rows is a bordered Cholesky:
- *     B = Yk Yp^T,  Lkp = B Lp^-T,  T = I + Yk Yk^T - Lkp Lkp^T = Lkk Lkk^T,  Zk = T^-1 Rt,  Zp = -Lp^-T (Lkp^T Zk),
- *     U = (Zk^T Yk + Zp^T Yp) X,  W = W0 + float(U)
- * and the rows Yk, [Lkp Lkk] (and the inverses of the diagonal tiles they touch) are written behind row M of the caller's state. */
-int64_t emcid_edit_dual_preserve_workspace_bytes(int64_t N, int64_t d, int64_t h, int64_t capacity) {
-    if (N <= 0 || d <= 0 || h <= 0 || capacity < N) return 0;
-    return PreserveWorkspace(N, d, h, capacity).total * (int64_t)sizeof(double);
-}
-
-int emcid_edit_layer_dual_preserve_f64(const float* K, const float* Zc, const float* zs_t, int64_t N, int64_t d, int64_t h,
-                                       double edit_weight, int layers_left, double lam_ratio, const void* cov_factor_ws,
-                                       int64_t n_layers, int64_t layer_index, double* Yp, int64_t ldy, double* Lp, int64_t ldl,
-                                       double* tile_inv, int64_t capacity, int64_t M, const float* W0, float* W, float* dW_out,
-                                       double* U_out, void* workspace, int64_t workspace_bytes, int* info_dev, void* stream) {
-    EMCID_CHECK_ARG(N > 0 && d > 0 && h > 0 && Yp && Lp && tile_inv && workspace && info_dev && cov_factor_ws);
-    EMCID_CHECK_ARG(0 <= layer_index && layer_index < n_layers && (W || dW_out || U_out) && ((W == nullptr) || (W0 != nullptr)));
-    EMCID_CHECK_ARG(session_state_ok(M, N, d, Yp, ldy, Lp, ldl, tile_inv, capacity));
-    PreserveWorkspace pw(N, d, h, capacity);
-    const DualWorkspace& ws = pw.dual;
-    if (workspace_bytes < pw.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    // Kt64, Rt and Yt = Kt64 X^T, exactly as the plain apply-only form
-    EMCID_TRY(emcid_edit_dual_apply_stage1_f64(K, Zc, zs_t, N, d, h, edit_weight, layers_left, lam_ratio, cov_factor_ws, n_layers,
-                                               layer_index, 0, N, 1, workspace, ws.total * (int64_t)sizeof(double), stream));
-    double* base = (double*)workspace;
-    const KeyHalf k = pw.key_half(base);
-    double *R = base + ws.off_R, *RT = base + ws.off_PT, *Y2 = base + ws.off_Y2, *V = base + ws.off_V, *U = base + ws.off_U;
-    double *ZT = base + pw.off_ZT, *G = base + pw.off_G;
-    const int64_t dp = ws.dp, Np = ws.Np, cp = pw.cp;
-    double* Lkp = Lp + M * ldl;
-    EMCID_TRY(session_append_rows(k, N, Yp, ldy, Lp, ldl, tile_inv, M, info_dev, st, __func__));
-    // RT[h, Np] = Rt^T ; Zk^T = RT T^-1
-    EMCID_TRY(solve_schur_rhs(R, ws.hp, h, Np, k.LS, k.invS, cholesky_takes_shadow(Np) ? k.XT : nullptr, k.S, RT, Y2, st));
-    // ZT = [Zp^T | Zk^T] [h, M + N]: then V = ZT [Yp; Yk] is ONE product over the state's rows, the new ones included
-    hipLaunchKernelGGL(copy2d_f64_kernel, dim3((unsigned)h), dim3(256), 0, st, RT, Np, ZT + M, cp, (int)h, (int)N, 1.0);
-    if (M > 0) {
-        {
-            ScopedProf sp(KC_DELTA_W, st);       // G[h, M] = -(Zk^T Lkp)
-            GemmShape g{RT, Np, Lkp, ldl, (int)h, (int)M, (int)N, 0};
-            launch_gemm_f64<true, false>(g, EpiAxpby{G, cp, -1.0, 0.0}, st);
-        }
-        trsm_tiles_backward(Lp, ldl, tile_inv, M, G, cp, ZT, cp, (int)h, st);      // Zp^T = G Lp^-1
-    }
-    {
-        ScopedProf sp(KC_DELTA_W, st);           // V[h, dp] = Zp^T Yp + Zk^T Yk
-        GemmShape g{ZT, cp, Yp, ldy, (int)h, (int)dp, (int)(M + N), 0};
-        launch_gemm_f64<true, false>(g, EpiAxpby{V, dp, 1.0, 0.0}, st);
-    }
-    apply_inverse_backward(cov_inverse(cov_factor_ws, n_layers, dp, layer_index), dp, V, (int)h, (int)dp, U, dp, st, base + ws.off_SK);
-    if (W || dW_out) hipLaunchKernelGGL(apply_u2d_kernel, dim3((unsigned)h), dim3(256), 0, st, U, dp, W0, W, dW_out, (int)d);
-    if (U_out) hipLaunchKernelGGL(copy2d_f64_kernel, dim3((unsigned)h), dim3(256), 0, st, U, dp, U_out, d, (int)h, (int)d, 1.0);
-    EMCID_CHECK_LAUNCH();
-    return EMCID_OK;
-}
-
-/* ---- edit sessions: a RETAIN list — preserved rows with a zero residual -------------------------------------------------------
- * The first half of emcid_edit_layer_dual_preserve_f64 for keys that are to stay where they are: Yk, B, Lkp, T, its Cholesky and
- * the append behind row M.  With Rt = 0 the step's Zk, Zp and U vanish identically, so that half is not run at all: no Zc, no
- * targets, no weights. */
-int64_t emcid_session_retain_workspace_bytes(int64_t N, int64_t d, int64_t capacity) {
-    if (N <= 0 || d <= 0 || capacity < N) return 0;
-    return RetainWorkspace(N, d, capacity).total * (int64_t)sizeof(double);
-}
-
-int emcid_session_retain_f64(const float* K, int64_t N, int64_t d, double row_scale, double lam_ratio, const void* cov_factor_ws,
-                             int64_t n_layers, int64_t layer_index, double* Yp, int64_t ldy, double* Lp, int64_t ldl,
-                             double* tile_inv, int64_t capacity, int64_t M, void* workspace, int64_t workspace_bytes, int* info_dev,
-                             void* stream) {
-    EMCID_CHECK_ARG(K && N > 0 && d > 0 && Yp && Lp && tile_inv && workspace && info_dev && cov_factor_ws);
-    EMCID_CHECK_ARG(0 <= layer_index && layer_index < n_layers && row_scale > 0.0 && row_scale < 1e150);
-    EMCID_CHECK_ARG(lam_ratio > 0.0 && lam_ratio < 1e300);
-    EMCID_CHECK_ARG(session_state_ok(M, N, d, Yp, ldy, Lp, ldl, tile_inv, capacity));
-    RetainWorkspace ws(N, d, capacity);
-    if (workspace_bytes < ws.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    double* base = (double*)workspace;
-    double *Kt = base + ws.off_K, *Yt = base + ws.off_Y;
-    const int64_t dp = ws.dp, Np = ws.Np;
-    {
-        ScopedProf sp(KC_PREP, st);
-        hipLaunchKernelGGL(prep_k_kernel, dim3((unsigned)Np), dim3(256), 0, st, K, (int)N, (int)d, row_scale, Kt, (int)dp,
-                           1.0 / sqrt(lam_ratio));
-    }
-    // Yt = Kt64 X^T over the Np padded rows, as stage 1 of the apply-only form runs the whole concept range
-    apply_inverse_forward(cov_inverse(cov_factor_ws, n_layers, dp, layer_index), dp, Kt, Yt, (int)Np, st, base + ws.off_SK);
-    return session_append_rows(ws.key_half(base), N, Yp, ldy, Lp, ldl, tile_inv, M, info_dev, st, __func__);
-}
-
-/* ---- edit sessions: RELEASE rows of the preserved set ----------------------------------------------------------------------------
- * keep[0 .. n_keep) are the rows that stay, ascending, keep[j] == j below `first` (the smallest released index).  Rows < first of
- * Yp, Lp and the tile inverses already are the state of the reduced set (the leading rows of a Cholesky factor do not depend on
- * later ones).  The kept rows behind `first` are gathered into the workspace's Yt block — source and destination rows overlap in
- * Yp — and re-enter as the key half of a step with M = first, N = n_keep - first: no forward, no X, no statistics, no weights. */
-int64_t emcid_session_release_workspace_bytes(int64_t n_rebuilt, int64_t d, int64_t capacity) {
-    return emcid_session_retain_workspace_bytes(n_rebuilt, d, capacity);
-}
-
-int emcid_session_release_f64(const int32_t* keep_dev, int64_t n_keep, int64_t first, int64_t d, double* Yp, int64_t ldy, double* Lp,
-                              int64_t ldl, double* tile_inv, int64_t capacity, int64_t M, void* workspace, int64_t workspace_bytes,
-                              int* info_dev, void* stream) {
-    EMCID_CHECK_ARG(keep_dev && d > 0 && Yp && Lp && tile_inv && workspace && aligned16(workspace) && info_dev);
-    EMCID_CHECK_ARG(first < n_keep && n_keep < M && M <= capacity);
-    const int64_t N = n_keep - first;
-    EMCID_CHECK_ARG(session_state_ok(first, N, d, Yp, ldy, Lp, ldl, tile_inv, capacity));
-    RetainWorkspace ws(N, d, capacity);
-    if (workspace_bytes < ws.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    double* base = (double*)workspace;
-    hipLaunchKernelGGL(gather_rows_f64_kernel, dim3((unsigned)ws.Np), dim3(256), 0, st, Yp, ldy, keep_dev + first, (int)N, (int)M,
-                       base + ws.off_Y, (int)ws.dp);
-    return session_append_rows(ws.key_half(base), N, Yp, ldy, Lp, ldl, tile_inv, first, info_dev, st, __func__);
-}
-
-/* The readout of the preserve step that has just run on `workspace` (same N, d, h, capacity, M, same stream): the step left
- * ZT = [Zp^T | Zk^T] [h][M + N] and Rt [N][h] there.  One launch. */
-int emcid_session_step_norms_f64(const void* workspace, int64_t workspace_bytes, int64_t N, int64_t d, int64_t h, int64_t capacity,
-                                 int64_t M, double* drift_out, double* left_out, double* resid_out, void* stream) {
-    EMCID_CHECK_ARG(workspace && N > 0 && d > 0 && h > 0 && left_out && resid_out && (drift_out || M == 0));
-    EMCID_CHECK_ARG(M >= 0 && M + N <= capacity && capacity < (int64_t)1 << 30);
-    PreserveWorkspace pw(N, d, h, capacity);
-    if (workspace_bytes < pw.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
-    const double* base = (const double*)workspace;
-    const double *R = base + pw.dual.off_R, *ZT = base + pw.off_ZT;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(step_norms_kernel, dim3((unsigned)((M + 2 * N + 3) / 4)), dim3(256), 0, st, ZT, pw.cp, R, pw.dual.hp, (int)h,
-                       (int)M, (int)N, drift_out, left_out, resid_out);
-    EMCID_CHECK_LAUNCH();
-    return EMCID_OK;
-}
-
-/* ---- dual solver, apply-only form, COLUMN-SHARDED over ranks (multi-GPU) -----------------------------------
- * The d columns of Yt = Kt64 X^T are dealt to the ranks in 128-wide tiles (`tiles`: this rank's tile indices, ascending).
- * With Yc = the rank's columns of Yt:
- *     S = I + sum_ranks Yc Yc^T        (one all-reduce of the N x N partial sums — the only coupling of the concepts)
- *     V[:, mine] = Z^T Yc,  Z = S^-1 Rt (every rank factors S itself: d^3-free, latency-bound, 0.5 ms)
- *     U = V X = sum_ranks V[:, mine] X[mine, :]      (one all-reduce of the h x d partial sums)
- * so a rank's GEMM work is 1/world of the layer's and nothing but S and U crosses the links.  Needs X = inv(L) of the layer
- * (emcid_cov_inverse_f64).  stage 1 leaves the partial S (no identity) at emcid_edit_dual_s(); stage 2 expects the SUMMED S
- * there and leaves the partial U (leading dimension dp = d rounded up to 128) at emcid_edit_dual_u(). */
-__global__ __launch_bounds__(256) void add_identity_f64_kernel(double* __restrict__ S, int n) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) S[(int64_t)i * n + i] += 1.0;
-}
-
-static int check_tiles(const int* tiles, int n_tiles, int64_t dp) {
-    if (!tiles || n_tiles <= 0 || n_tiles > 256) return 0;
-    for (int i = 0; i < n_tiles; ++i)
-        if (tiles[i] < 0 || (int64_t)tiles[i] * NB >= dp || (i > 0 && tiles[i] <= tiles[i - 1])) return 0;
-    return 1;
-}
-
-int emcid_edit_dual_cols_stage1_f64(const float* K, const float* Zc, const float* zs_t, int64_t N, int64_t d, int64_t h,
-                                    double edit_weight, int layers_left, double lam_ratio, const void* cov_factor_ws, int64_t n_layers,
-                                    int64_t layer_index, const int* tiles_host, int n_tiles, void* workspace,
-                                    int64_t workspace_bytes, void* stream) {
-    EMCID_CHECK_ARG(K && Zc && zs_t && N > 0 && d > 0 && h > 0 && layers_left > 0 && cov_factor_ws && workspace);
-    EMCID_CHECK_ARG(0 <= layer_index && layer_index < n_layers && lam_ratio > 0.0 && lam_ratio < 1e300);
-    DualWorkspace ws(N, d, h);
-    EMCID_CHECK_ARG(check_tiles(tiles_host, n_tiles, ws.dp));
-    if (workspace_bytes < ws.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    double* base = (double*)workspace;
-    double *Kt = base + ws.off_K, *Yc = base + ws.off_Y, *R = base + ws.off_R, *S = base + ws.off_S, *sk = base + ws.off_SK;
-    const int64_t dp = ws.dp, Np = ws.Np;
-    const double* X = cov_inverse(cov_factor_ws, n_layers, dp, layer_index);
-    const double s = sqrt(edit_weight / 0.5);
-    {
-        ScopedProf sp(KC_PREP, st);
-        hipLaunchKernelGGL(prep_kr_kernel, dim3((unsigned)Np), dim3(256), 0, st, K, Zc, zs_t, (int)N, (int)d, (int)h, s,
-                           (double)layers_left, Kt, (int)Np, (int)dp, R, (int)ws.hp, 1.0 / sqrt(lam_ratio));
-    }
-    for (int i = 0; i < n_tiles; ++i) {        // Yc[:, 128 i : 128 i + 128] = Kt[:, 0 : kd] X[128 t : 128 t + 128, 0 : kd]^T,  kd = 128 (t + 1)
-        const int64_t t = tiles_host[i], kd = (t + 1) * NB;
-        ScopedProf sp(KC_INV_APPLY, st);
-        GemmShape g{Kt, dp, X + t * NB * dp, dp, (int)Np, NB, (int)kd, 0};
-        if (!launch_gemm_f64_streamk2<true, true>(g, EpiAxpby{Yc + (int64_t)i * NB, dp, 1.0, 0.0}, st, kStreamKWgs, sk))
-            return fail(EMCID_ERR_BAD_ARG, __func__, "more output tiles than stream-K ticket counters");
-    }
-    {   // partial S = Yc Yc^T on the lower 128-tiles, K = 128 n_tiles deep
-        ScopedProf sp(KC_ASSEMBLE, st);
-        GemmShape g{Yc, dp, Yc, dp, (int)Np, (int)Np, n_tiles * NB, 1};
-        if (!launch_gemm_f64_streamk2<true, true>(g, EpiAxpby{S, Np, 1.0, 0.0}, st, kStreamKWgs, sk, 0.0))
-            return fail(EMCID_ERR_BAD_ARG, __func__, "more output tiles than stream-K ticket counters");
-    }
-    EMCID_CHECK_LAUNCH();
-    return EMCID_OK;
-}
-
-double* emcid_edit_dual_s(void* workspace, int64_t N, int64_t d, int64_t h) {
-    if (!workspace || N <= 0 || d <= 0 || h <= 0) return nullptr;
-    return (double*)workspace + DualWorkspace(N, d, h).off_S;
-}
-
-double* emcid_edit_dual_u(void* workspace, int64_t N, int64_t d, int64_t h) {
-    if (!workspace || N <= 0 || d <= 0 || h <= 0) return nullptr;
-    return (double*)workspace + DualWorkspace(N, d, h).off_U;
-}
-
-int emcid_edit_dual_cols_stage2_f64(int64_t N, int64_t d, int64_t h, const void* cov_factor_ws, int64_t n_layers,
-                                    int64_t layer_index, const int* tiles_host, int n_tiles, void* workspace,
-                                    int64_t workspace_bytes, int* info_dev, void* stream) {
-    EMCID_CHECK_ARG(N > 0 && d > 0 && h > 0 && workspace && info_dev && cov_factor_ws);
-    EMCID_CHECK_ARG(0 <= layer_index && layer_index < n_layers);
-    DualWorkspace ws(N, d, h);
-    EMCID_CHECK_ARG(check_tiles(tiles_host, n_tiles, ws.dp));
-    if (workspace_bytes < ws.total * (int64_t)sizeof(double)) return fail(EMCID_ERR_WORKSPACE, __func__, "workspace too small");
-    hipStream_t st = (hipStream_t)stream;
-    double* base = (double*)workspace;
-    double *Yc = base + ws.off_Y, *R = base + ws.off_R, *S = base + ws.off_S, *LS = base + ws.off_LS, *invS = base + ws.off_invS;
-    double *RT = base + ws.off_PT, *Y2 = base + ws.off_Y2, *V = base + ws.off_V, *U = base + ws.off_U;
-    const int64_t dp = ws.dp, Np = ws.Np, hp = ws.hp;
-    const double* X = cov_inverse(cov_factor_ws, n_layers, dp, layer_index);
-    const int w = n_tiles * NB;
-    const bool xrow = cholesky_takes_shadow(Np);
-    EMCID_TRY(with_graph(make_key(8, {Yc, R, S, LS, RT, V, U, info_dev}, {dp, Np, N, hp, (int64_t)w + ((int64_t)xrow << 40)}), st, [&](hipStream_t q) {
-        hipLaunchKernelGGL(add_identity_f64_kernel, dim3((unsigned)((Np + 255) / 256)), dim3(256), 0, q, S, (int)Np);
-        const XrowJob xj{base + ws.off_XT, Np, base + ws.off_TT};
-        EMCID_TRY(cholesky_impl(S, LS, Np, Np, invS, info_dev, q, nullptr, xrow ? &xj : nullptr));
-        // RT := Z^T, against the inverse that rode in the factorization or by substitution
-        EMCID_TRY(solve_schur_rhs(R, hp, h, Np, LS, invS, xrow ? xj.Xt : nullptr, nullptr, RT, Y2, q));
-        {
-            ScopedProf sp(KC_DELTA_W, q);       // V[h, w] = Z^T Yc
-            GemmShape g{RT, Np, Yc, dp, (int)h, w, (int)Np, 0};
-            launch_gemm_f64<true, false>(g, EpiAxpby{V, dp, 1.0, 0.0}, q);
-        }
-        hipLaunchKernelGGL(zero2d_f64_kernel, dim3((unsigned)h, 1u), dim3(256), 0, q, U, dp, (int64_t)0, (int)dp);
-        return check_launch("emcid_edit_dual_cols_stage2_f64");
-    }));
-    for (int i = 0; i < n_tiles; ++i) {        // U[:, 0 : kd] += V[:, 128 i : 128 i + 128] X[128 t : 128 t + 128, 0 : kd]
-        const int64_t t = tiles_host[i], kd = (t + 1) * NB;
-        ScopedProf sp(KC_INV_APPLY, st);
-        GemmShape g{V + (int64_t)i * NB, dp, X + t * NB * dp, dp, (int)h, (int)kd, NB, 0};
-        launch_gemm_f64<true, false>(g, EpiAxpby{U, dp, 1.0, 1.0}, st);
-    }
-    EMCID_CHECK_LAUNCH();
-    return EMCID_OK;
-}
-
-/* W = W0 + float(U) (optional), dW = float(U) (optional) for U [h][ldu] f64 with ldu >= d (the padded partial sums above) */
-int emcid_apply_update2d_f32(const double* U, int64_t ldu, const float* W0, float* W, float* dW, int64_t h, int64_t d, void* stream) {
-    EMCID_CHECK_ARG(U && h > 0 && d > 0 && ldu >= d && (W || dW) && ((W == nullptr) || (W0 != nullptr)));
-    hipLaunchKernelGGL(apply_u2d_kernel, dim3((unsigned)h), dim3(256), 0, (hipStream_t)stream, U, ldu, W0, W, dW, (int)d);
-    EMCID_CHECK_LAUNCH();
-    return EMCID_OK;
 }
 
 }  // extern "C"

@@ -10,7 +10,7 @@ weights.  That dependency is exactly the order of a single forward pass, so here
            K  = gather_mean(fc2 input)                 # HIP, csrc/gram_f32.hip
            Zc = gather_mean(fc2 output)                # pre-edit output, bias included (as :1002-1016)
            [all-gather K, Zc over concept shards]      # RCCL, multi-GPU only
-           W  = W0 + float(R X^T)                      # HIP fp64 MFMA solve, csrc/spd_solve.hip
+           W  = W0 + float(R X^T)                      # HIP fp64 MFMA solve, csrc/edit_solve.hip on csrc/spd_solve.hip
            return fc2(input) with the NEW W            # the rest of the pass sees the edited layer
       └─ the hook of the last edited layer aborts the pass (nothing downstream is needed)
 

@@ -48,7 +48,7 @@ def test_release_workspace_is_the_retain_workspace_of_the_rebuilt_rows():
 
 
 def test_workspace_blocks_hold_a_rebuild_close_to_the_capacity():
-    """N = capacity - 1: every block the shared tail addresses lies inside the workspace.  The blocks, in doubles (csrc/spd_solve.hip,
+    """N = capacity - 1: every block the shared tail addresses lies inside the workspace.  The blocks, in doubles (csrc/session.hip,
     RetainWorkspace): K and Y [Np, dp], S, LS, XT [Np, Np], TT [Np, 128], B [Np, cp] with Np <= cp — B's rows are cp wide and the tail
     writes columns < first <= capacity - N of N <= Np rows; the total is at least their sum."""
     lib = hip.load()
