@@ -1,6 +1,7 @@
 // Edit sessions on the apply-only dual form (edit_solve.hip): a layer keeps the keys of earlier steps in factor coordinates, and a
 // step is a bordered Cholesky behind them.  Preserve (an edit's rows), retain (rows with a zero residual), release (rows leave,
-// the rest is rebuilt), the per-step readout, and the fold of a full preserved set into a covariance factor of its own.
+// the rest is rebuilt), the per-step readout, the fold of a full preserved set into a covariance factor of its own, and the release of
+// rows a fold has taken (the same rows subtracted from the folded system, all layers refactored in one batched chain).
 #include "spd_solve.h"
 
 namespace emcid {
@@ -241,6 +242,86 @@ __global__ __launch_bounds__(256) void fold_copy_lower_kernel(const double* __re
     }
 }
 
+// base -= sum_r a_r a_r^T over the released rows a_r = archive[rel_idx[r]] on one NB x NB tile of the block lower triangle, and
+// the tile written twice: to base and to the M region the factorization consumes (the fold's third copy launch, fused).  256
+// threads as 16 x 16, a thread holds rows 8 ty .. 8 ty + 7 and the double2 columns 2 tx + 32 c (c < 4) in registers; the two
+// 128-wide segments of DD_ROWS released rows at a time go through LDS (2 x DD_ROWS x 1 KiB = 32 KiB; at ~236 VGPRs two
+// workgroups share a compute unit, 64 of its 160 KiB, and one loads while the other multiplies; the a_i reads are one address
+// per 16 lanes, the a_j reads 16 bytes per lane in lane order).  An index outside [0, n_rows), and the tail of the last chunk,
+// enter as zeros.  n_rel = 0: the copy alone.
+constexpr int DD_ROWS = 16;
+__global__ __launch_bounds__(256) void fold_downdate_kernel(const double* __restrict__ archive, int64_t lda,
+                                                            const int32_t* __restrict__ rel_idx, int n_rel, int n_rows,
+                                                            double* __restrict__ base, double* __restrict__ Mb, int dp) {
+    int I, J;
+    lower_tile_of((int)blockIdx.x, I, J);
+    __shared__ __align__(16) double S[2][DD_ROWS][NB];      // [0]: the tile's row segment of a released row, [1]: its column segment
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    double2 acc[8][4];
+    for (int r = 0; r < 8; ++r)
+        for (int c = 0; c < 4; ++c)
+            acc[r][c] = *reinterpret_cast<const double2*>(base + (int64_t)(I * NB + 8 * ty + r) * dp + J * NB + 2 * tx + 32 * c);
+    for (int k0 = 0; k0 < n_rel; k0 += DD_ROWS) {
+        __syncthreads();      // (the chunk before has been consumed)
+        for (int e = threadIdx.x; e < DD_ROWS * NB; e += 256) {        // DD_ROWS x (64 + 64) double2
+            const int rr = e / NB, seg = (e % NB) / (NB / 2), c2 = e % (NB / 2);
+            const int k = k0 + rr;
+            const int row = k < n_rel ? rel_idx[k] : -1;
+            double2 v = make_double2(0.0, 0.0);
+            if (row >= 0 && row < n_rows)
+                v = *reinterpret_cast<const double2*>(archive + (int64_t)row * lda + (seg ? J : I) * NB + 2 * c2);
+            *reinterpret_cast<double2*>(&S[seg][rr][2 * c2]) = v;
+        }
+        __syncthreads();
+#pragma unroll 2
+        for (int rr = 0; rr < DD_ROWS; ++rr) {
+            double a[8];
+            double2 b[4];
+            for (int q = 0; q < 4; ++q) {
+                const double2 t = *reinterpret_cast<const double2*>(&S[0][rr][8 * ty + 2 * q]);
+                a[2 * q] = t.x;
+                a[2 * q + 1] = t.y;
+            }
+            for (int c = 0; c < 4; ++c) b[c] = *reinterpret_cast<const double2*>(&S[1][rr][2 * tx + 32 * c]);
+            for (int r = 0; r < 8; ++r)
+                for (int c = 0; c < 4; ++c) {
+                    acc[r][c].x -= a[r] * b[c].x;
+                    acc[r][c].y -= a[r] * b[c].y;
+                }
+        }
+    }
+    for (int r = 0; r < 8; ++r)
+        for (int c = 0; c < 4; ++c) {
+            const int64_t at = (int64_t)(I * NB + 8 * ty + r) * dp + J * NB + 2 * tx + 32 * c;
+            *reinterpret_cast<double2*>(base + at) = acc[r][c];
+            *reinterpret_cast<double2*>(Mb + at) = acc[r][c];
+        }
+}
+
+// The first two stages of a fold, for one layer: the M preserved keys back from factor coordinates, Q [M][ldq] = Yp L_s^T against
+// a clean lower-triangular copy of L_s = gain Lsrc in the M region Mb, then base += Q^T Q on the lower tiles (C != null: base
+// filled from the statistics first).  Q stays where it is written: a fold's scratch, or the tail of a session's archive.
+static void fold_rows_into_base(const double* Lsrc, double gain, const double* Yp, int64_t ldy, int64_t M, int64_t dp, double* Mb,
+                                double* Q, int64_t ldq, double* base, const float* C, int64_t d, double lam, float cw,
+                                hipStream_t st) {
+    const int64_t nt = dp / NB;
+    const unsigned n_tri = (unsigned)(nt * (nt + 1) / 2);
+    hipLaunchKernelGGL(fold_copy_lower_kernel, dim3(n_tri), dim3(256), 0, st, Lsrc, Mb, (int)dp, gain, 1);
+    {
+        ScopedProf sp(KC_INV_APPLY, st);
+        GemmShape g{Yp, ldy, Mb, dp, (int)M, (int)dp, (int)dp, 0};
+        g.tri = 1;       // B(k, n) = L_s[n][k], zero for k > n
+        g.pair = 1;
+        launch_gemm_f64<true, true>(g, EpiAxpby{Q, ldq, 1.0, 0.0}, st, 2);
+    }
+    if (C) hipLaunchKernelGGL(fold_base_fill_kernel, dim3(n_tri), dim3(256), 0, st, C, (int)d, (int)dp, lam, cw, base);
+    {
+        ScopedProf sp(KC_ASSEMBLE, st);      // base += Q^T Q on the lower tiles: both operands stored [K = M][dp]
+        GemmShape g{Q, ldq, Q, ldq, (int)dp, (int)dp, (int)M, 1};
+        launch_gemm_f64<false, false>(g, EpiAxpby{base, dp, 1.0, 1.0}, st);
+    }
+}
+
 int64_t emcid_cov_factor_fold_workspace_bytes(int64_t M, int64_t d) {
     if (M <= 0 || d <= 0) return 0;
     return M * round_up(d, NB) * (int64_t)sizeof(double);          // Q = Yp L_s^T [M, dp]
@@ -262,31 +343,56 @@ int emcid_cov_factor_fold_f64(const void* src_ws, double lam_ratio, const double
     EMCID_CHECK_ARG(ldy >= dp && ldy % 2 == 0);
     EMCID_CHECK_WORKSPACE(workspace_bytes, emcid_cov_factor_fold_workspace_bytes(M, d), " (see emcid_cov_factor_fold_workspace_bytes)");
     hipStream_t st = (hipStream_t)stream;
-    const double* Lsrc = cov.L(src_ws, layer_index);
     double* Mb = cov.M(dst_ws, layer_index);                 // consumed by the factorization; scratch before and after
     double *Lb = cov.L(dst_ws, layer_index), *Ib = cov.I(dst_ws, layer_index), *Xb = cov.X(dst_ws, layer_index);
-    double* Q = (double*)workspace;
-    const unsigned n_tri = (unsigned)(nt * (nt + 1) / 2);
-    // the keys back from factor coordinates: Q = Yp L_s^T against a clean lower-triangular copy of L_s in the M region
-    hipLaunchKernelGGL(fold_copy_lower_kernel, dim3(n_tri), dim3(256), 0, st, Lsrc, Mb, (int)dp, sqrt(lam_ratio), 1);
-    {
-        ScopedProf sp(KC_INV_APPLY, st);
-        GemmShape g{Yp, ldy, Mb, dp, (int)M, (int)dp, (int)dp, 0};
-        g.tri = 1;       // B(k, n) = L_s[n][k], zero for k > n
-        g.pair = 1;
-        launch_gemm_f64<true, true>(g, EpiAxpby{Q, dp, 1.0, 0.0}, st, 2);
-    }
-    if (fill_base)
-        hipLaunchKernelGGL(fold_base_fill_kernel, dim3(n_tri), dim3(256), 0, st, C, (int)d, (int)dp, lam, (float)(1.0 - edit_weight),
-                           base);
-    {
-        ScopedProf sp(KC_ASSEMBLE, st);      // base += Q^T Q on the lower tiles: both operands stored [K = M][dp]
-        GemmShape g{Q, dp, Q, dp, (int)dp, (int)dp, (int)M, 1};
-        launch_gemm_f64<false, false>(g, EpiAxpby{base, dp, 1.0, 1.0}, st);
-    }
-    hipLaunchKernelGGL(fold_copy_lower_kernel, dim3(n_tri), dim3(256), 0, st, base, Mb, (int)dp, 1.0, 0);
+    fold_rows_into_base(cov.L(src_ws, layer_index), sqrt(lam_ratio), Yp, ldy, M, dp, Mb, (double*)workspace, dp, base,
+                        fill_base ? C : nullptr, d, lam, (float)(1.0 - edit_weight), st);
+    hipLaunchKernelGGL(fold_copy_lower_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, st, base, Mb, (int)dp, 1.0, 0);
     EMCID_TRY(cholesky_serial(Mb, Lb, dp, dp, Ib, info_dev, st, 1, cov.s_mat, cov.s_inv));
     EMCID_TRY(build_full_inverse(Lb, dp, dp, Ib, Xb, Mb, 1, cov.s_mat, cov.s_inv, st));
+    EMCID_CHECK_LAUNCH();
+    return EMCID_OK;
+}
+
+/* ---- release across a fold (edit sessions that keep the rows their folds added) ------------------------------------------------
+ * A fold adds q_i q_i^T for the rows Q = Yp L_s^T it leaves in its scratch; a session that keeps those rows (its ARCHIVE, [rows][lda]
+ * fp64) releases folded ones without a Cholesky downdate: subtract the same q_i q_i^T from base and factor base again.  The
+ * update entry does, for ONE layer, in place on the session's own workspace at lam_ratio 1: the M live rows into the archive's
+ * tail as Q (a fold's first two stages), then base -= the released rows, archived and just-added alike, through one index list,
+ * the result copied to the layer's M region.  The refactor entry then factors the M regions of ALL layers as one batched chain. */
+int emcid_session_refold_update_f64(void* cov_ws, int64_t n_layers, int64_t d, int64_t layer_index, const double* Yp, int64_t ldy,
+                                    int64_t M, int64_t capacity, double* archive, int64_t lda, int64_t n_archived,
+                                    const int32_t* rel_idx_dev, int64_t n_rel, double* base, void* stream) {
+    EMCID_CHECK_ARG(cov_ws && archive && base && n_layers > 0 && n_layers <= 32 && d > 0 && d <= 32768);
+    EMCID_CHECK_ARG(0 <= layer_index && layer_index < n_layers);
+    EMCID_CHECK_ARG(M >= 0 && M <= capacity && capacity < (int64_t)1 << 30 && n_rel >= 0 && M + n_rel > 0);
+    EMCID_CHECK_ARG(n_archived >= 0 && n_archived + M < (int64_t)1 << 31 && n_rel < (int64_t)1 << 31);
+    EMCID_CHECK_ARG((M == 0 || Yp) && (n_rel == 0 || rel_idx_dev));
+    const CovFactorLayout cov(n_layers, d);
+    const int64_t dp = cov.dp, nt = dp / NB;
+    EMCID_CHECK_ARG(aligned16(cov_ws) && aligned16(Yp) && aligned16(archive) && aligned16(base));
+    EMCID_CHECK_ARG(lda >= dp && lda % 2 == 0 && (M == 0 || (ldy >= dp && ldy % 2 == 0)));
+    hipStream_t st = (hipStream_t)stream;
+    double* Mb = cov.M(cov_ws, layer_index);
+    if (M > 0)
+        fold_rows_into_base(cov.L(cov_ws, layer_index), 1.0, Yp, ldy, M, dp, Mb, archive + n_archived * lda, lda, base, nullptr, d,
+                            0.0, 0.0f, st);
+    {
+        ScopedProf sp(KC_ASSEMBLE, st);
+        hipLaunchKernelGGL(fold_downdate_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, st, archive, lda, rel_idx_dev,
+                           (int)n_rel, (int)(n_archived + M), base, Mb, (int)dp);
+    }
+    EMCID_CHECK_LAUNCH();
+    return EMCID_OK;
+}
+
+int emcid_cov_factor_refactor_f64(void* cov_ws, int64_t workspace_bytes, int64_t n_layers, int64_t d, int* info_dev, void* stream) {
+    EMCID_CHECK_ARG(cov_ws && info_dev && n_layers > 0 && n_layers <= 32 && d > 0 && d <= 32768 && aligned16(cov_ws));
+    const CovFactorLayout cov(n_layers, d);
+    EMCID_CHECK_WORKSPACE(workspace_bytes, cov.total * (int64_t)sizeof(double), " (see emcid_cov_factor_workspace_bytes)");
+    // every layer at once, as emcid_factor_cov_f64 runs them; eagerly: the chain is the session's, once per release
+    EMCID_TRY(cholesky_serial(cov.M(cov_ws, 0), cov.L(cov_ws, 0), cov.dp, cov.dp, cov.I(cov_ws, 0), info_dev, (hipStream_t)stream,
+                              (int)n_layers, cov.s_mat, cov.s_inv));
     EMCID_CHECK_LAUNCH();
     return EMCID_OK;
 }

@@ -5,7 +5,7 @@
 //                     the one place the fp64 GEMM kernels are instantiated
 //   gemm_f64_api.hip  the C entries of the fp64 GEMM family
 //   edit_solve.hip    primal solver, covariance-factor workspace, the dual / apply-only / column-sharded forms
-//   session.hip       edit sessions: preserve, retain, release, step norms, fold
+//   session.hip       edit sessions: preserve, retain, release, step norms, fold, release across a fold
 #pragma once
 #include "common.h"
 #include "gemm_f64.h"

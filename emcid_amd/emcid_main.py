@@ -684,6 +684,26 @@ def release_plan(ledger, folded_sources, sources):
     return keep, first, retained
 
 
+def refold_plan(ledger, archive_ledger, sources):
+    """The host half of a release that reaches across a fold (``EditSession(keep_folded=True).release``), pure: ``ledger`` as in
+    ``release_plan``, ``archive_ledger`` the same tuples for the rows the folds archived, in archive order, ``sources`` the names
+    to release.  Returns (archived: ascending indices into the archive of the rows that go, live: ascending indices into the ledger
+    of the rows that go, retained: how many of either a retain list had added).  A name with live AND archived rows loses all of
+    them.  ``ValueError`` for an empty list, ``KeyError`` for a name found in neither ledger."""
+    names = list(sources)
+    if not names:
+        raise ValueError("a release needs at least one source")
+    known = {row[0] for row in ledger} | {row[0] for row in archive_ledger}
+    for name in names:
+        if name not in known:
+            raise KeyError(f"source {name!r} has no preserved row in this session, live or folded")
+    gone = set(names)
+    archived = [i for i, row in enumerate(archive_ledger) if row[0] in gone]
+    live = [i for i, row in enumerate(ledger) if row[0] in gone]
+    retained = sum(1 for rows in (ledger, archive_ledger) for row in rows if row[0] in gone and row[1] == "retain")
+    return archived, live, retained
+
+
 class EditSession:
     """A sequence of ``apply_emcid_to_text_encoder`` calls on ONE text encoder in which every later edit keeps the keys of the
     earlier ones: step t solves against lam C' + P^T P + Kt^T Kt, P the stacked (scaled) keys of steps < t, where two plain calls
@@ -699,6 +719,7 @@ class EditSession:
         sess.rows(); sess.sources()               # the ledger: (source, "edit" | "retain", ordinal, token) per row; what release() can take
         sess.fold()                               # take the M preserved rows into the session's own base factor: M -> 0
         sess.folded                               # rows folded so far (still preserved, exactly)
+        sess.folded_sources()                     # keep_folded=True: the names release() can take back out of the folds
         sess.reset()                              # forget the preserved keys (the weights stay as they are)
         sess.restore()                            # the weights of before the first step back, and the keys forgotten
 
@@ -740,7 +761,25 @@ class EditSession:
     [first, M) and the touched tile inverses of every layer are copied first; all layers run, ONE pinned flag read decides, and a
     non-zero flag puts the copy back and raises ``torch.linalg.LinAlgError`` with nothing released.  ``retained`` drops by the
     retained rows released; a stored ``report()`` readout is dropped (``None`` until the next step).  A fold empties the ledger:
-    folded sources live inside the base factor and cannot be released (``ValueError``; ``restore()`` starts over).
+    folded sources live inside the base factor and cannot be released (``ValueError``; ``restore()`` starts over) — unless the
+    session keeps what its folds added:
+
+    ``keep_folded=True`` makes every fold (``fold()``, the automatic one of ``on_full="fold"``, the chunked ones of ``retain``)
+    ARCHIVE its rows: a fold adds q_i q_i^T to ``base`` for the rows Q = Yp L^T, and writes Q into the tail of a session-owned fp64
+    archive (n_layers tensors [rows, dp], grown geometrically) instead of a scratch buffer — no further launch, no copy; the ledger
+    entries move into an archive ledger (``folded_sources()``) while ``rows()`` / ``sources()`` still list live rows only.
+    ``release`` of a name with archived rows is then a REFOLD, with no Cholesky downdate: per edited layer the M live rows join the
+    archive as Q and ``base`` += Q^T Q (``hip.session_refold_update``: a fold's first two stages), ``base`` -= q_i q_i^T for the
+    released rows, archived and just-added live ones alike, and ``base`` is factored again — all layers in ONE batched chain
+    (``hip.cov_factor_refactor``) where a fold runs one serial chain per layer.  ONE pinned flag read decides, like ``fold()``:
+    zero commits everything together (M -> 0: the live set is folded as a side effect, exactly preserved and still releasable;
+    the archive and its ledger are compacted; ``folded`` = folded + M_kept - released archived rows; ``folds`` += 1; ``released`` /
+    ``retained`` adjusted; the stored ``report()`` dropped), non-zero puts the private workspace and ``base`` back from the copies
+    taken first, leaves the archive's length alone and raises ``torch.linalg.LinAlgError`` with nothing released.  No weight is
+    read or written.  A release that names live rows only is the plain one above.  Subtracting q_i q_i^T reverses the addition up to
+    the rounding of ``base``: ~1e-15 of max|L| on the factor when lam C' carries the system, ~1e-13 when the keys outweigh it 30 x
+    (DESIGN.md §3).  Cost of the archive: folded x dp doubles per edited layer — 45 MB per layer per full fold (1 843 rows) at
+    d = 3 072 — held until ``reset()`` / ``restore()``, which drop it.  The default (``False``) allocates and launches what it did.
 
     ``report=True`` adds one launch per edited layer to a step (``hip.session_step_norms``, from what the step left in its
     workspace: with Z = (I + Y Y^T)^-1 [0; Rt] the step moves preserved key i by dW p_i = -Zp_i and leaves Zk_j of residual j);
@@ -758,7 +797,8 @@ class EditSession:
     non-positive pivot restores the weights and raises ``torch.linalg.LinAlgError``."""
 
     def __init__(self, pipe, hparams: EMCIDHyperParams, device: Optional[str] = None, stats_dir=STATS_DIR,
-                 capacity: Optional[int] = None, verbose: bool = False, on_full: str = "raise", report: bool = False):
+                 capacity: Optional[int] = None, verbose: bool = False, on_full: str = "raise", report: bool = False,
+                 keep_folded: bool = False):
         if on_full not in ("raise", "fold"):
             raise ValueError(f"on_full must be 'raise' or 'fold' (got {on_full!r})")
         if isinstance(hparams, EMCIDXLHyperParams) or getattr(pipe, "text_encoder_2", None) is not None:
@@ -808,6 +848,10 @@ class EditSession:
         self._retains = 0                                    # retain() calls so far (the ordinal of a retained row)
         self._release_ws: Optional[hip.ReleaseWorkspace] = None
         self.released = 0                                    # rows released so far
+        self.keep_folded = bool(keep_folded)
+        self._archive: Optional[List[torch.Tensor]] = None   # keep_folded: per edited layer (rows, dp) f64, the Q rows every fold added
+        self._archived = 0                                   # rows of the archive that count (== folded on a keep_folded session)
+        self._archive_ledger: List[tuple] = []               # their ledger entries, in archive order
 
     @property
     def preserved(self) -> int:
@@ -834,9 +878,13 @@ class EditSession:
             dst, base = src, self._base
             keep = (dst.buf.clone(), base.clone())          # (a refused fold puts both back)
         dst.info.zero_()
-        ws = torch.empty(M * dst.dp, dtype=torch.float64, device=dev)
+        if self.keep_folded:                        # Q lands in the archive's tail: the fold entry leaves it there
+            self._archive_room(M, dst.dp, dev)
+            tails = [a[self._archived:self._archived + M].view(-1) for a in self._archive]
+        else:
+            tails = [torch.empty(M * dst.dp, dtype=torch.float64, device=dev)] * len(layers)
         for i in range(len(layers)):
-            hip.cov_factor_fold(src, self.keys, i, self._shared[1][i] if first else None, lam, e, dst, base, ws=ws)
+            hip.cov_factor_fold(src, self.keys, i, self._shared[1][i] if first else None, lam, e, dst, base, ws=tails[i])
         code = self._read_flag(dst.info)
         if code != 0:
             if keep is not None:
@@ -849,7 +897,11 @@ class EditSession:
                 f"the weights are as they were")
         self.private_factors, self._base = dst, base
         self.keys.reset()
-        self._folded_sources.update(row[0] for row in self._ledger)
+        if self.keep_folded:
+            self._archive_ledger += self._ledger
+            self._archived += M
+        else:
+            self._folded_sources.update(row[0] for row in self._ledger)
         self._ledger = []
         self.folded += M
         self.folds += 1
@@ -857,6 +909,19 @@ class EditSession:
         LP["session_folds"], LP["session_folded_rows"], LP["session_preserved_rows"] = self.folds, self.folded, 0
         if self.verbose:
             print(f"Session fold {self.folds}: {M} preserved rows folded into the base factor, {self.folded} folded so far")
+
+    def _archive_room(self, M: int, dp: int, dev):
+        """Make the archive of every edited layer hold ``M`` more rows: at least doubled when it has to grow (the rows that count
+        are copied over), allocated at the first fold that keeps its rows."""
+        need = self._archived + M
+        if self._archive is None:
+            self._archive = [torch.zeros(need, dp, dtype=torch.float64, device=dev) for _ in self._fixed[2]]
+        elif self._archive[0].shape[0] < need:
+            rows = max(need, 2 * self._archive[0].shape[0])
+            for i, old in enumerate(self._archive):
+                new = torch.zeros(rows, dp, dtype=torch.float64, device=dev)
+                new[:self._archived].copy_(old[:self._archived])
+                self._archive[i] = new
 
     def workspace(self, N: int, d: int, h: int, dev, retain: bool = False):
         """(engine side) the workspace of a step (``retain``: of a retain call) of N rows; the two most recent sizes keep theirs"""
@@ -1068,14 +1133,23 @@ class EditSession:
         """The distinct sources that ``release`` can take, in the order they first entered."""
         return list(dict.fromkeys(row[0] for row in self._ledger))
 
+    def folded_sources(self) -> List[str]:
+        """The distinct sources whose rows the folds of a ``keep_folded`` session archived, in the order they first entered: what
+        ``release`` can take back out of the base factor.  Empty on a default session."""
+        return list(dict.fromkeys(row[0] for row in self._archive_ledger))
+
     def release(self, sources, shard=None) -> int:
         """Take every live row of ``sources`` (``request["source"]`` strings, or request dicts) out of the preserved set — all
         ``num_edit_tokens`` rows of a request, every occurrence of a source entered more than once — so that the concept can be
         edited again, or is no longer held (class docstring).  No weight changes.  Returns the rows released.  ``KeyError``: a source
         without a preserved row; ``ValueError``: a folded source, an empty list, and what ``apply`` refuses; all before anything is
-        launched or allocated.  A non-positive pivot raises ``torch.linalg.LinAlgError`` with the state as it was."""
+        launched or allocated.  A non-positive pivot raises ``torch.linalg.LinAlgError`` with the state as it was.  On a
+        ``keep_folded`` session a folded source goes too: the release is then a refold of every edited layer (class docstring),
+        which takes the live rows into the base factor on its way (``preserved`` is 0 afterwards)."""
         names = [s["source"] if isinstance(s, dict) else s for s in sources]
         self._check_call(names or [None], shard, "a release")
+        if self.keep_folded and names and not {row[0] for row in self._archive_ledger}.isdisjoint(names):
+            return self._release_refold(names)
         keep, first, n_retained = release_plan(self._ledger, self._folded_sources, names)
         M, kept = self.preserved, len(keep)
         assert M == len(self._ledger)
@@ -1119,6 +1193,58 @@ class EditSession:
                 f"release after step {self.steps}: the system of the {n_rebuilt} kept rows behind row {first} is not positive definite "
                 f"(non-positive pivot at column {code - 1}); the {M} preserved rows are as they were and nothing was released")
 
+    def _release_refold(self, names) -> int:
+        """A release that names archived rows: update every edited layer's ``base`` (``hip.session_refold_update``), factor all of
+        them in one batched chain (``hip.cov_factor_refactor``), ONE pinned flag read, then commit or put everything back."""
+        arch, live, n_retained = refold_plan(self._ledger, self._archive_ledger, names)
+        keys, fac, base, n0 = self.keys, self.private_factors, self._base, self._archived
+        M = self.preserved
+        assert M == len(self._ledger) and n0 == len(self._archive_ledger) and fac is not None
+        dev = fac.buf.device
+        rel = arch + [n0 + i for i in live]
+        if M > 0:
+            self._archive_room(M, fac.dp, dev)
+        rel_dev = torch.tensor(rel, dtype=torch.int32, device=dev)
+        keep = (fac.buf.clone(), base.clone())              # (a refused refold puts both back)
+        fac.info.zero_()
+        for i in range(keys.n_layers):
+            hip.session_refold_update(fac, keys, i, self._archive[i], n0, rel_dev, base)
+        hip.cov_factor_refactor(fac)
+        code = self._read_flag(fac.info)
+        if code != 0:
+            fac.buf.copy_(keep[0])
+            base.copy_(keep[1])
+            fac.info.zero_()
+            fac.have_inverse = set(range(fac.n_layers))
+            raise torch.linalg.LinAlgError(
+                f"release after step {self.steps}: the folded system without the {len(rel)} released rows is not positive definite "
+                f"(non-positive pivot at column {code - 1}); the {M} preserved and {n0} folded rows, the private factors and the "
+                f"weights are as they were and nothing was released")
+        del keep
+        gone = set(rel)
+        stay = [k for k in range(rel[0], n0 + M) if k not in gone]      # (rows below the first released one stay where they are)
+        if stay:
+            idx = torch.tensor(stay, dtype=torch.long, device=dev)
+            for a in self._archive:
+                a[rel[0]:rel[0] + len(stay)] = a.index_select(0, idx)
+        both = self._archive_ledger + self._ledger
+        self._archive_ledger = both[:rel[0]] + [both[k] for k in stay]
+        self._archived = len(self._archive_ledger)
+        self._ledger = []
+        keys.reset()
+        self.folded += (M - len(live)) - len(arch)
+        self.folds += 1
+        self.retained -= n_retained
+        self.released += len(rel)
+        self._report = self._report_pending = None
+        LP = clip_forward.LAST_PATHS
+        LP["session_released_rows"], LP["session_preserved_rows"], LP["session_retained_rows"] = self.released, 0, self.retained
+        LP["session_folds"], LP["session_folded_rows"] = self.folds, self.folded
+        if self.verbose:
+            print(f"Session release: {len(arch)} folded and {len(live)} live rows of {len(set(names))} sources released by a refold, "
+                  f"{self.folded} folded")
+        return len(rel)
+
     def reset(self):
         """Forget the preserved keys; the weights stay as they are, the next step starts a fresh set (M = 0)."""
         if self.keys is not None:
@@ -1128,6 +1254,7 @@ class EditSession:
         self.folded = self.folds = self.retained = self.released = self._retains = 0
         self._report = self._report_pending = None
         self._ledger, self._folded_sources, self._release_ws = [], set(), None
+        self._archive, self._archived, self._archive_ledger = None, 0, []
         LP = clip_forward.LAST_PATHS
         LP["session_steps"] = LP["session_preserved_rows"] = LP["session_folds"] = LP["session_folded_rows"] = 0
         LP["session_retained_rows"] = LP["session_released_rows"] = 0

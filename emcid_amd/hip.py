@@ -32,6 +32,7 @@ EXPORTS = [
     "emcid_session_retain_workspace_bytes", "emcid_session_retain_f64", "emcid_session_step_norms_f64",
     "emcid_session_release_workspace_bytes", "emcid_session_release_f64",
     "emcid_cov_factor_fold_workspace_bytes", "emcid_cov_factor_fold_f64",
+    "emcid_session_refold_update_f64", "emcid_cov_factor_refactor_f64",
     "emcid_edit_lu_workspace_bytes", "emcid_edit_layer_lu_f64", "emcid_lu_solve_f64",
     "emcid_edit_dual_cols_stage1_f64", "emcid_edit_dual_s", "emcid_edit_dual_u", "emcid_edit_dual_cols_stage2_f64",
     "emcid_apply_update2d_f32", "emcid_linear_f32", "emcid_linear_ws_f32", "emcid_linear_workspace_bytes",
@@ -102,6 +103,8 @@ def load():
         "emcid_session_release_f64": (i32, [p, i64, i64, i64, p, i64, p, i64, p, i64, i64, p, i64, p, p]),
         "emcid_cov_factor_fold_workspace_bytes": (i64, [i64, i64]),
         "emcid_cov_factor_fold_f64": (i32, [p, f64, p, i64, i64, i64, p, f64, f64, i32, p, i64, i64, i64, p, p, i64, p, p]),
+        "emcid_session_refold_update_f64": (i32, [p, i64, i64, i64, p, i64, i64, i64, p, i64, i64, p, i64, p, p]),
+        "emcid_cov_factor_refactor_f64": (i32, [p, i64, i64, i64, p, p]),
         "emcid_cholesky_solve_f64": (i32, [p, i64, i64, p, p, p, i64, i64, p]),
         "emcid_edit_dual_cols_stage1_f64": (i32, [p, p, p, i64, i64, i64, f64, i32, f64, p, i64, i64, p, i32, p, i64, p]),
         "emcid_edit_dual_s": (p, [p, i64, i64, i64]),
@@ -1501,3 +1504,52 @@ def cov_factor_fold(src: CovFactors, state: PreservedKeys, layer_index: int, cov
     dst.have_inverse.add(int(layer_index))
     dst.lam, dst.edit_weight, dst.cached = float(lam), float(edit_weight), False
     return dst
+
+
+def _check_own_workspace(factors: CovFactors, who: str):
+    if factors.cached:
+        raise EmcidHipError(f"{who}: the workspace belongs to the factor cache; a refold writes only into a workspace its caller owns")
+
+
+def session_refold_update(factors: CovFactors, state: PreservedKeys, layer_index: int, archive: torch.Tensor, n_archived: int,
+                          rel_idx: Optional[torch.Tensor], base: torch.Tensor):
+    """The update half of a release across a fold for layer ``layer_index`` (include/emcid_hip.h, emcid_session_refold_update_f64),
+    in place on ``factors``, the caller's OWN workspace (never one of the factor cache) whose lam is the session's: the ``state.M``
+    live rows go into rows [n_archived, n_archived + M) of ``archive`` (rows, dp) f64 as Q = Yp L^T, ``base`` (n_layers, dp, dp) f64
+    += Q^T Q, then ``base`` -= the rows ``rel_idx`` names (int32 on the device, indices into the n_archived + M rows the archive
+    holds by then; ``None``: no row goes) and the result lands in the layer's M region for ``cov_factor_refactor``.  L, X and the
+    state are only read and ``have_inverse`` stays as it is: the workspace is whole until the refactorization runs.  Asynchronous
+    on the current stream; nothing is committed here (the caller counts the archive's new rows once the flag read zero)."""
+    _check_own_workspace(factors, "session_refold_update")
+    if state.d != factors.d:
+        raise EmcidHipError(f"refold: the workspace (d = {factors.d}) and the state (d = {state.d}) must describe the same layers")
+    dp, M, n_archived = factors.dp, int(state.M), int(n_archived)
+    if base.dtype != torch.float64 or not base.is_contiguous() or base.numel() != factors.n_layers * dp * dp:
+        raise EmcidHipError(f"refold: base must be a contiguous f64 tensor of {factors.n_layers} x {dp} x {dp}")
+    if archive.dtype != torch.float64 or archive.dim() != 2 or archive.stride(1) != 1 or archive.shape[1] < dp or \
+            n_archived < 0 or archive.shape[0] < n_archived + M:
+        raise EmcidHipError(f"refold: the archive must be an f64 tensor of at least {n_archived + M} rows of {dp} (got "
+                            f"{tuple(archive.shape)}, {archive.dtype})")
+    n_rel = 0 if rel_idx is None else int(rel_idx.numel())
+    if n_rel and (rel_idx.dtype != torch.int32 or not rel_idx.is_contiguous() or rel_idx.device != archive.device):
+        raise EmcidHipError(f"refold: rel_idx must be a contiguous int32 tensor on {archive.device}")
+    in_range = 0 <= layer_index < state.n_layers        # (a layer outside the state: the library refuses the call)
+    Yp, ldy = state.layer_args(layer_index if in_range else 0)[:2]
+    base_l = base.view(factors.n_layers, dp, dp)[layer_index if in_range and layer_index < factors.n_layers else 0]
+    _check(load().emcid_session_refold_update_f64(
+        _ptr(factors.buf), factors.n_layers, factors.d, int(layer_index), Yp, ldy, M, state.capacity,
+        _ptr(archive, torch.float64, "archive"), archive.stride(0), n_archived, _ptr(rel_idx) if n_rel else None, n_rel,
+        _ptr(base_l, torch.float64, "base"), _stream(factors.buf)), "emcid_session_refold_update_f64")
+
+
+def cov_factor_refactor(factors: CovFactors) -> CovFactors:
+    """Factor the M regions of every layer of ``factors`` — the caller's OWN workspace, after ``session_refold_update`` on each
+    layer — as one batched chain and build every X = inv(L) (emcid_cov_factor_refactor_f64, then ``cov_inverse``).  Asynchronous
+    on the current stream; ``factors.info`` reports a non-positive pivot.  ``have_inverse`` is emptied by the factorization and
+    filled again by the inverse build."""
+    _check_own_workspace(factors, "cov_factor_refactor")
+    _check(load().emcid_cov_factor_refactor_f64(_ptr(factors.buf), factors.nbytes, factors.n_layers, factors.d,
+                                                _ptr(factors.info, torch.int32), _stream(factors.buf)), "emcid_cov_factor_refactor_f64")
+    factors.have_inverse = set()
+    cov_inverse(factors)
+    return factors

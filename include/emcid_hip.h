@@ -458,6 +458,30 @@ int emcid_cov_factor_fold_f64(const void* src_ws, double lam_ratio, const double
                               int64_t d, int64_t layer_index, double* base, void* workspace, int64_t workspace_bytes,
                               int* info_dev, void* stream);
 
+/* Release ACROSS a fold (entry points added under ABI 16; edit sessions that keep the rows their folds added).  A fold adds
+ * q_i q_i^T to base for the rows Q = Yp L_s^T it leaves in its workspace; a caller that keeps them (its ARCHIVE: [rows][lda] fp64,
+ * lda >= dp and even, padding columns zero as the fold writes them) takes folded rows out again with no Cholesky downdate:
+ * subtract the same q_i q_i^T from base and factor base again.
+ * emcid_session_refold_update_f64, ONE layer per call, in place on the caller's OWN workspace cov_ws at lam_ratio 1, no host
+ * synchronisation, no info word, no workspace (the archive is state):
+ *     M > 0:  a fold's first two stages: the clean lower copy of L into the layer's M region, Q = Yp L^T written to
+ *             archive + n_archived * lda (M rows), base += Q^T Q on the lower 128 x 128 tiles
+ *     then    base -= sum_r a_r a_r^T,  a_r = archive[rel_idx_dev[r]],  r < n_rel: indices into the n_archived + M rows the archive
+ *             holds by now, archived and just-added alike; an index outside [0, n_archived + M) contributes nothing; each lower
+ *             tile is written once to base and once to the layer's M region (whole diagonal tiles, as the fold's copy leaves them)
+ * M = 0 with n_rel > 0 and n_rel = 0 with M > 0 are both valid (not both zero); 0 <= M <= capacity.  Yp, L, X and the block
+ * inverses are only read: until the refactor entry has run the workspace still serves a step.  The caller bumps n_archived by M
+ * (and compacts the archive) only once the refactorization was sound.
+ * emcid_cov_factor_refactor_f64 factors the M regions of ALL layers as they are, one batched chain (the launches of
+ * emcid_factor_cov_f64 without the fill, issued eagerly): L and the block inverses of every layer; X = inv(L) comes from
+ * emcid_cov_inverse_f64(cov_ws, n_layers, d, 0, n_layers) next.  workspace_bytes: emcid_cov_factor_workspace_bytes(n_layers, d),
+ * refused with EMCID_ERR_WORKSPACE when short.  info_dev reports a non-positive pivot like emcid_factor_cov_f64; the caller
+ * then puts its copies of the workspace and of base back. */
+int emcid_session_refold_update_f64(void* cov_ws, int64_t n_layers, int64_t d, int64_t layer_index, const double* Yp, int64_t ldy,
+                                    int64_t M, int64_t capacity, double* archive, int64_t lda, int64_t n_archived,
+                                    const int32_t* rel_idx_dev, int64_t n_rel, double* base, void* stream);
+int emcid_cov_factor_refactor_f64(void* cov_ws, int64_t workspace_bytes, int64_t n_layers, int64_t d, int* info_dev, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Fallback with the reference's own solver semantics.  torch.linalg.solve (reference: emcid/emcid_main.py:1045-1048) is
  * LAPACK getrf + getrs: LU with partial pivoting, which returns numbers for ANY nonsingular system, whereas the Cholesky
