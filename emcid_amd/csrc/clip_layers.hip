@@ -91,6 +91,14 @@ __global__ __launch_bounds__(256) void fingerprint_store_kernel(FpBatch b, long 
     }
 }
 
+// The same fingerprint without the address: word blockIdx.x of the batch's slot range of `out` (edit sessions compare these across
+// processes, where a table entry's pointer means nothing).
+__global__ __launch_bounds__(256) void fingerprint_content_kernel(FpBatch b, unsigned long long* out) {
+    __shared__ unsigned long long lds[4];
+    const unsigned long long h = fingerprint_of(b.data[blockIdx.x], b.bytes[blockIdx.x], lds);
+    if (threadIdx.x == 0) out[b.slot[blockIdx.x]] = h;
+}
+
 struct FpSkip { unsigned long long m[4]; };                   // bit b of word w: slot first_slot + 64 w + b is not to be looked at
 
 __global__ __launch_bounds__(256) void fingerprint_check_kernel(const long long* table, long long first_slot, FpSkip skip, int* flag) {
@@ -179,6 +187,26 @@ int emcid_fingerprint_check(const void* table, int64_t table_slots, int64_t firs
         for (int w = 0; w < 4; ++w) skip.m[w] = skip_mask[w];
     hipLaunchKernelGGL(fingerprint_check_kernel, dim3((unsigned)n_slots), dim3(256), 0, (hipStream_t)stream, (const long long*)table,
                        (long long)first_slot, skip, flag);
+    EMCID_CHECK_LAUNCH();
+    return EMCID_OK;
+}
+
+/* include/emcid_hip.h, "content fingerprint": out_dev[i] = the fingerprint emcid_fingerprint_store computes for tensor i, and
+ * nothing of its address.  One launch per 32 tensors, one workgroup per tensor (host arrays). */
+int emcid_fingerprint_content(int64_t n, const void* const* data, const int64_t* bytes, uint64_t* out_dev, void* stream) {
+    EMCID_CHECK_ARG(n >= 0 && (n == 0 || (data && bytes && out_dev)));
+    if (n == 0) return EMCID_OK;
+    for (int64_t i = 0; i < n; ++i)        // (all of them before the first launch: a refused call has written nothing)
+        EMCID_CHECK_ARG(data[i] && bytes[i] > 0 && bytes[i] % 16 == 0 && aligned16(data[i]));
+    for (int64_t i0 = 0; i0 < n; i0 += 32) {
+        FpBatch b{};
+        const int cnt = (int)std::min<int64_t>(32, n - i0);
+        for (int i = 0; i < cnt; ++i) {
+            b.data[i] = (const unsigned char*)data[i0 + i]; b.bytes[i] = bytes[i0 + i]; b.slot[i] = i0 + i;
+        }
+        hipLaunchKernelGGL(fingerprint_content_kernel, dim3((unsigned)cnt), dim3(256), 0, (hipStream_t)stream, b,
+                           (unsigned long long*)out_dev);
+    }
     EMCID_CHECK_LAUNCH();
     return EMCID_OK;
 }

@@ -634,6 +634,30 @@ def _dual_factors(plan: EncoderEditPlan, form: str, dev):
     return fac_done, lazy
 
 
+def _cache_own_factors(plan: EncoderEditPlan):
+    """Hand the factors a plan made itself (``factor_key`` set) to the factor cache, once their flag word read zero."""
+    if plan.factor_key is not None and plan.cov_factors is not None and _factor_cache_size() > 0:
+        with ENGINE_LOCK:
+            plan.cov_factors.cached = True
+            _FACTOR_CACHE[plan.factor_key] = (plan.cov_factors, [plan.covs[l] for l in plan.layers])
+            while len(_FACTOR_CACHE) > _factor_cache_size():
+                _FACTOR_CACHE.popitem(last=False)
+        plan.factor_key = None
+
+
+def session_factors(text_encoder, layers, rewrite_module_tmp: str, lam: float, edit_weight: float, covs: Dict[int, torch.Tensor], dev):
+    """The factors of lam C' of every edited layer with their explicit inverses, obtained the way a session step obtains them
+    (``_dual_factors``: the factor cache under the key plain calls use, else one batched factorization on the side stream) but
+    without a pass — what ``emcid_main.EditSession.load`` takes as the coordinates of the rows it loads.  The current stream waits
+    for them.  Returns (factors, commit): ``commit()``, to be called once the caller has read ``factors.info`` as zero, hands
+    factors made here to the cache as ``check_info`` does (nothing to do after a cache hit)."""
+    plan = EncoderEditPlan(text_encoder, list(layers), rewrite_module_tmp, float(lam), float(edit_weight), None, None, covs, 0)
+    fac_done, _ = _dual_factors(plan, "dual_preserve", dev)
+    if fac_done is not None:
+        torch.cuda.current_stream(dev).wait_stream(plan.side_stream)
+    return plan.cov_factors, lambda: _cache_own_factors(plan)
+
+
 def _finish_inverse_factors(plan: EncoderEditPlan, dev):
     """After a pass that factored lam * C' itself: build the explicit inverse factors it did not need (off the critical path,
     on the side stream) so that check_info can hand the complete set to later edits."""
@@ -1079,13 +1103,7 @@ def check_info(plan: EncoderEditPlan, restore_on_failure: bool = True):
             f"lam*C + K K^T is singular to working precision (zero pivot at column {code - 1} of the pivoted LU): "
             f"torch.linalg.solve (reference emcid_main.py:1045) raises for this system too; the edited weights have been restored")
     if code == 0:
-        if plan.factor_key is not None and plan.cov_factors is not None and _factor_cache_size() > 0:
-            with ENGINE_LOCK:
-                plan.cov_factors.cached = True
-                _FACTOR_CACHE[plan.factor_key] = (plan.cov_factors, [plan.covs[l] for l in plan.layers])
-                while len(_FACTOR_CACHE) > _factor_cache_size():
-                    _FACTOR_CACHE.popitem(last=False)
-            plan.factor_key = None
+        _cache_own_factors(plan)
         return
     if plan.factor_key is not None:
         plan.factor_key = None

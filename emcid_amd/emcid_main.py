@@ -704,6 +704,105 @@ def refold_plan(ledger, archive_ledger, sources):
     return archived, live, retained
 
 
+SESSION_FORMAT = 1     # of the file EditSession.save writes ("session file"); load refuses any other
+_SESSION_ENTRIES = ("fixed", "rewrite_module_tmp", "d", "h", "capacity", "on_full", "report", "keep_folded", "counters", "ledger",
+                    "folded_sources", "archive_ledger", "keys", "weights", "orig", "base", "archive", "fingerprints")
+_SESSION_COUNTERS = ("steps", "folds", "folded", "retained", "released", "retains")
+
+
+def check_session_state(state, fixed=None, rewrite_module_tmp=None, d=None, h=None, capacity=None) -> int:
+    """The host half of ``EditSession.load``, pure: is ``state`` (the dict of a session file) whole and consistent in itself —
+    format version, every tensor's shape and dtype against M / d / h / the layers, the ledger's length against M, the archive and
+    its ledger against ``folded``, ``base`` present exactly when rows were folded — and, for the arguments that are given, does it
+    agree with the session it is to continue: ``fixed`` (mom2_update_weight, edit_weight, layers, num_edit_tokens),
+    ``rewrite_module_tmp``, ``d``, ``h``, and ``capacity`` >= M (default: the file's own).  Returns M; ``ValueError`` naming what is
+    wrong otherwise.  No tensor's contents are read."""
+    if not isinstance(state, dict) or "format" not in state:
+        raise ValueError("not a session file: a dict with a 'format' entry is expected")
+    if state["format"] != SESSION_FORMAT:
+        raise ValueError(f"session file of unknown format {state['format']!r} (this version reads format {SESSION_FORMAT})")
+    missing = [k for k in _SESSION_ENTRIES if k not in state]
+    if missing:
+        raise ValueError(f"session file without the entries {missing}")
+    fx = state["fixed"]
+    saved = (float(fx["mom2_update_weight"]), float(fx["edit_weight"]), tuple(fx["layers"]), int(fx["num_edit_tokens"]))
+    if fixed is not None and tuple(fixed) != saved:
+        raise ValueError(f"the session was saved with (mom2_update_weight, edit_weight, layers, num_edit_tokens) = {saved}, the hparams "
+                         f"say {tuple(fixed)}: a loaded session continues with the values it was opened with")
+    if rewrite_module_tmp is not None and rewrite_module_tmp != state["rewrite_module_tmp"]:
+        raise ValueError(f"the session was saved for the weights {state['rewrite_module_tmp']!r}, the hparams name {rewrite_module_tmp!r}")
+    for name, given in (("d", d), ("h", h)):
+        if isinstance(state[name], bool) or not isinstance(state[name], int) or state[name] < 1:
+            raise ValueError(f"session file: {name} must be a positive integer (got {state[name]!r})")
+        if given is not None and int(given) != state[name]:
+            raise ValueError(f"the session was saved for edited weights with {name} = {state[name]}, this encoder's have {name} = {given}")
+    L, sd, sh = len(saved[2]), state["d"], state["h"]
+    dp = (sd + hip.NB - 1) // hip.NB * hip.NB
+    cap = state["capacity"] if capacity is None else capacity
+    try:
+        M = hip.check_preserved_state(state["keys"], L, sd, cap)
+    except hip.EmcidHipError as e:
+        raise ValueError(f"session file: {e}") from e
+    counters = state["counters"]
+    for k in _SESSION_COUNTERS:
+        if isinstance(counters.get(k), bool) or not isinstance(counters.get(k), int) or counters[k] < 0:
+            raise ValueError(f"session file: counter {k!r} must be a non-negative integer (got {counters.get(k)!r})")
+    folded = counters["folded"]
+    if len(state["ledger"]) != M:
+        raise ValueError(f"session file: the ledger lists {len(state['ledger'])} rows, the state holds M = {M}")
+
+    def tensors(name, shape, dtype, rows_at_least=None):
+        ts = state[name]
+        if not isinstance(ts, (list, tuple)) or len(ts) != L:
+            raise ValueError(f"session file: {name} must be a list of {L} tensors, one per edited layer")
+        for i, t in enumerate(ts):
+            ok = isinstance(t, torch.Tensor) and t.dtype == dtype and t.dim() == len(shape) and tuple(t.shape[1:]) == tuple(shape[1:])
+            if ok and rows_at_least is None:
+                ok = t.shape[0] == shape[0]
+            if not ok:
+                got = (tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"session file: {name}[{i}] must be a {dtype} tensor of {tuple(shape)} (got {got})")
+            if rows_at_least is not None and t.shape[0] < rows_at_least:
+                raise ValueError(f"session file: {name}[{i}] holds {t.shape[0]} rows, {rows_at_least} were folded")
+
+    tensors("weights", (sh, sd), torch.float32)
+    if state["orig"] is not None:
+        tensors("orig", (sh, sd), torch.float32)
+    base = state["base"]
+    if (base is None) != (counters["folds"] == 0):
+        raise ValueError(f"session file: {counters['folds']} folds, but the folded systems (base) are {'missing' if base is None else 'there'}")
+    if base is not None and not (isinstance(base, torch.Tensor) and base.dtype == torch.float64 and tuple(base.shape) == (L, dp, dp)):
+        raise ValueError(f"session file: base must be an f64 tensor of {(L, dp, dp)}")
+    if state["keep_folded"]:
+        if len(state["archive_ledger"]) != folded:
+            raise ValueError(f"session file: the archive's ledger lists {len(state['archive_ledger'])} rows, {folded} were folded")
+        if folded > 0 or state["archive"] is not None:
+            tensors("archive", (folded, dp), torch.float64, rows_at_least=folded)
+    elif state["archive"] is not None or len(state["archive_ledger"]):
+        raise ValueError("session file: an archive on a session that does not keep what its folds added")
+    return M
+
+
+def _read_session_file(path) -> dict:
+    """The dict of a session file: tensors and plain Python values only (``weights_only``), all on the host."""
+    return torch.load(str(path), map_location="cpu", weights_only=True)
+
+
+def _write_session_file(state: dict, path) -> int:
+    """``torch.save`` to a temporary name beside ``path``, then renamed over it: an interrupted save leaves the previous file
+    whole.  Returns the bytes written."""
+    path = Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    tmp = path.with_name(f".{path.name}.{os.getpid()}.tmp")
+    try:
+        torch.save(state, str(tmp))
+        os.replace(tmp, path)
+    finally:
+        if tmp.exists():
+            tmp.unlink()
+    return path.stat().st_size
+
+
 class EditSession:
     """A sequence of ``apply_emcid_to_text_encoder`` calls on ONE text encoder in which every later edit keeps the keys of the
     earlier ones: step t solves against lam C' + P^T P + Kt^T Kt, P the stacked (scaled) keys of steps < t, where two plain calls
@@ -722,6 +821,8 @@ class EditSession:
         sess.folded_sources()                     # keep_folded=True: the names release() can take back out of the folds
         sess.reset()                              # forget the preserved keys (the weights stay as they are)
         sess.restore()                            # the weights of before the first step back, and the keys forgotten
+        sess.save(path)                           # everything above to ONE file, between any two operations
+        EditSession.load(pipe, hparams, path)     # ... and a session that carries on from it, in another process
 
     A step is a warm call's chain with the dual stage swapped for ``hip.edit_layer_dual_preserve``: the factors of lam C' come
     from the engine's factor cache under the key plain calls use (a session never refactors), the earlier keys live in factor
@@ -780,6 +881,18 @@ class EditSession:
     the rounding of ``base``: ~1e-15 of max|L| on the factor when lam C' carries the system, ~1e-13 when the keys outweigh it 30 x
     (DESIGN.md §3).  Cost of the archive: folded x dp doubles per edited layer — 45 MB per layer per full fold (1 843 rows) at
     d = 3 072 — held until ``reset()`` / ``restore()``, which drop it.  The default (``False``) allocates and launches what it did.
+
+    SAVE / LOAD carry a session across processes.  ``save(path)`` writes the fixed set-up, counters and ledgers, the COMMITTED rows
+    of every layer without their padding or anything of the capacity (``hip.PreservedKeys.state_dict``: Yp[:M, :d], Lp[:M, :M], the
+    tile inverses rows < M touch), the edited weights as they are and as they were before the first step, ``base`` of a folded
+    session — not its factored workspace, four times the size and rebuilt by one batched chain (``hip.cov_factor_from_base``) —, the
+    counted rows of the archive, and a content fingerprint (``hip.fingerprint_content``: the stale-cache guard's word without the
+    address) of every other parameter of the encoder and of each edited layer's statistics; one synchronising copy, one file,
+    renamed into place.  ``load`` checks the file on the host (``check_session_state``), refuses another encoder, other statistics
+    or — ``weights="check"`` — other edited weights with ``ValueError`` and the encoder untouched, takes the factors of lam C' from
+    the engine's factor cache as a step does, allocates the state at ITS capacity (any value >= M) and copies the rows and tiles to
+    where that layout wants them; ONE pinned read decides.  The stored ``report()`` readout is not saved (``None`` until the next
+    step).  A session that is never saved or loaded allocates and launches what it did.
 
     ``report=True`` adds one launch per edited layer to a step (``hip.session_step_norms``, from what the step left in its
     workspace: with Z = (I + Y Y^T)^-1 [0; Rt] the step moves preserved key i by dW p_i = -Zp_i and leaves Zk_j of residual j);
@@ -1266,6 +1379,196 @@ class EditSession:
                 for l, w in self._weights().items():
                     w.copy_(self._orig[l])
         self.reset()
+
+    # ---- save to a file, resume in another process --------------------------------------------------------------------------
+
+    def _other_parameters(self):
+        """[(name, parameter)] of the text encoder outside the edited weights, in ``named_parameters`` order."""
+        edited = {id(w) for w in self._weights().values()}      # (by identity: nethook resolves names more freely than equality)
+        return [(n, p) for n, p in self.pipe.text_encoder.named_parameters() if id(p) not in edited]
+
+    def _statistics(self):
+        """[(layer name, statistics file, C in HBM)] per edited layer: the matrices a step of this session reads."""
+        from .layer_stats import stats_filename
+        hp, te = self.hparams, self.pipe.text_encoder
+        out = []
+        for l in self._fixed[2]:
+            name = hp.rewrite_module_tmp.format(l)
+            c = get_cov_text_encoder(te, self.pipe.tokenizer, name, hp.mom2_dataset, hp.mom2_n_samples, hp.mom2_dtype,
+                                     stat_dir=self.stats_dir, verbose=self.verbose)
+            out.append((name, str(stats_filename(self.stats_dir, "text_encoder", hp.mom2_dataset, name, hp.mom2_dtype, ["mom2"],
+                                                 3 * 1024, hp.mom2_n_samples)), c))
+        return out
+
+    def save(self, path) -> dict:
+        """Write everything a later process needs to carry this session on to ONE file (``torch.save`` of CPU tensors and plain
+        values; INTEGRATION.md, "session file"): the fixed set-up, the counters and ledgers, the committed rows of every layer in a
+        form that knows nothing of the capacity (``hip.PreservedKeys.state_dict``), the edited weights as they are and as they were
+        before the first step, ``base`` of a folded session (not its factored workspace: four times the size, and rebuilt by
+        ``load``), the counted rows of a ``keep_folded`` archive, and content fingerprints of every other parameter of the encoder
+        and of the statistics, so that ``load`` can refuse another encoder or other statistics.  May be called between any two
+        operations; the session is not changed.  One synchronising copy to the host; the file is written under a temporary name
+        beside ``path`` and renamed.  Returns {"rows", "folded", "archived", "bytes"}."""
+        weights = self._weights()
+        w0 = next(iter(weights.values()))
+        if not w0.is_cuda:
+            raise hip.EmcidHipError(f"the text encoder must live in HBM (got {w0.device}); there is no CPU path")
+        dev, (lam, e, layers, k) = w0.device, self._fixed
+        pending = []
+
+        def host(t: torch.Tensor) -> torch.Tensor:
+            out = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+            out.copy_(t.detach(), non_blocking=True)
+            pending.append(out)
+            return out
+
+        keys = self.keys if self.keys is not None else hip.PreservedKeys(len(layers), self.d, 1, "cpu")
+        others = self._other_parameters()
+        # (a session that has not run anything yet has read no statistics: nothing of it depends on them)
+        stats = self._statistics() if self._shared is not None or self.private_factors is not None else None
+        words = host(hip.fingerprint_content([p for _, p in others] + [c for _, _, c in stats or ()]))
+        state = {
+            "format": SESSION_FORMAT,
+            "fixed": {"mom2_update_weight": lam, "edit_weight": e, "layers": list(layers), "num_edit_tokens": k},
+            "rewrite_module_tmp": self.hparams.rewrite_module_tmp, "d": self.d, "h": self.h, "capacity": self.capacity,
+            "on_full": self.on_full, "report": self.report_on, "keep_folded": self.keep_folded,
+            "counters": {"steps": self.steps, "folds": self.folds, "folded": self.folded, "retained": self.retained,
+                         "released": self.released, "retains": self._retains},
+            "ledger": [tuple(r) for r in self._ledger], "folded_sources": sorted(self._folded_sources, key=repr),
+            "archive_ledger": [tuple(r) for r in self._archive_ledger],
+            "keys": keys.state_dict(sync=False),
+            "weights": [host(weights[l]) for l in layers],
+            "orig": [host(self._orig[l]) for l in layers] if self._orig is not None else None,
+            "base": host(self._base) if self._base is not None else None,
+            "archive": [host(a[:self._archived]) for a in self._archive] if self._archive is not None else None,
+        }
+        torch.cuda.current_stream(dev).synchronize()        # the ONE synchronisation: every copy above has landed
+        words = words.tolist()
+        state["fingerprints"] = {
+            "encoder": [(n, list(p.shape), str(p.dtype), words[i]) for i, (n, p) in enumerate(others)],
+            "statistics": None if stats is None else
+            [(n, f, list(c.shape), words[len(others) + i]) for i, (n, f, c) in enumerate(stats)]}
+        del pending
+        nbytes = _write_session_file(state, path)
+        if self.verbose:
+            print(f"Session saved to {path}: {self.preserved} preserved and {self.folded} folded rows, {nbytes} bytes")
+        return {"rows": self.preserved, "folded": self.folded, "archived": self._archived, "bytes": nbytes}
+
+    @classmethod
+    def load(cls, pipe, hparams: EMCIDHyperParams, path, device: Optional[str] = None, stats_dir=STATS_DIR,
+             capacity: Optional[int] = None, weights: str = "check", verbose: bool = False, on_full: Optional[str] = None,
+             report: Optional[bool] = None) -> "EditSession":
+        """The session ``save`` wrote to ``path``, carried on in this process on ``pipe``: every public attribute and listing is
+        the saved session's, the next step preserves what its next step would have preserved, ``restore()`` gives the weights of
+        before its first step.  The first four arguments are the constructor's; ``hparams`` must agree with the file's fixed set-up.
+        ``capacity``: default the file's; any value >= the saved M (the rows and tiles go where the new layout wants them).
+        ``on_full`` / ``report``: default the file's; ``keep_folded`` is the file's.  ``weights="check"``: the encoder's edited
+        weights must equal the file's bit for bit (``ValueError`` naming the first that differs); ``"load"``: the file's are copied
+        into the encoder, last of all.  In both modes every other parameter of the encoder and every edited layer's statistics
+        must have the fingerprint the file recorded (``ValueError`` naming the parameter, or the layer and its statistics file).
+        The factors of lam C' come from the engine's factor cache as for a step; a folded session's private factors are rebuilt
+        from ``base`` in one batched chain.  ONE pinned read of fingerprints, comparisons and flag follows; a non-positive pivot
+        raises ``torch.linalg.LinAlgError``.  Whatever is refused, the encoder's weights are as they were.  Refuses what ``apply``
+        refuses; everything the file alone can show to be wrong is refused before any device call (``check_session_state``)."""
+        if weights not in ("check", "load"):
+            raise ValueError(f"weights must be 'check' or 'load' (got {weights!r})")
+        state = _read_session_file(path)
+        check_session_state(state)                  # (whole in itself, before anything of it is used)
+        sess = cls(pipe, hparams, device, stats_dir, state["capacity"] if capacity is None else capacity, verbose,
+                   state["on_full"] if on_full is None else on_full, state["report"] if report is None else report,
+                   keep_folded=state["keep_folded"])
+        M = check_session_state(state, sess._fixed, hparams.rewrite_module_tmp, sess.d, sess.h, sess.capacity)
+        sess._check_call([None], None, "a load")
+        live = sess._weights()
+        w0 = next(iter(live.values()))
+        if not w0.is_cuda:
+            raise hip.EmcidHipError(f"the text encoder must live in HBM (got {w0.device}); there is no CPU path")
+        dev, (lam, e, layers, _) = w0.device, sess._fixed
+        counters, prints = state["counters"], state["fingerprints"]
+        others = sess._other_parameters()
+        saved = [(n, tuple(s), dt) for n, s, dt, _ in prints["encoder"]]
+        found = [(n, tuple(p.shape), str(p.dtype)) for n, p in others]
+        if saved != found:
+            odd = next((a[0] for a, b in zip(saved, found) if a != b), None)
+            if odd is None:                         # (one list is the other's beginning)
+                odd = max(saved, found, key=len)[min(len(saved), len(found))][0]
+            raise ValueError(f"the session was saved on another text encoder: parameter {odd!r} differs in name, shape or dtype")
+        stats = sess._statistics() if prints["statistics"] is not None else None
+        for (n, f, c), (sn, sf, shape, _) in zip(stats or (), prints["statistics"] or ()):
+            if n != sn or list(c.shape) != list(shape):
+                raise ValueError(f"layer {n}: the statistics of {f} have shape {tuple(c.shape)}, the session was saved with "
+                                 f"{tuple(shape)} for {sn} ({sf})")
+        # everything the device has to say, queued on the current stream and read back once
+        words = hip.fingerprint_content([p for _, p in others] + [c for _, _, c in stats or ()])
+        want = torch.tensor([w for *_, w in prints["encoder"]] + [w for *_, w in prints["statistics"] or ()], dtype=torch.int64)
+        differs = [words != want.to(dev, non_blocking=True)]
+        if weights == "check":
+            differs.append(torch.stack([(live[l].detach().view(torch.int32) != state["weights"][i].to(dev).view(torch.int32)).any()
+                                        for i, l in enumerate(layers)]))
+        private = base = commit = None
+        info = torch.zeros(1, dtype=torch.int32, device=dev)
+        if state["base"] is not None:
+            base = state["base"].to(dev)
+            private = hip.cov_factor_from_base(base, sess.d, lam, e)
+            shared, info = (private, [c for _, _, c in stats]), private.info
+        elif stats is not None:
+            fac, commit = edit_engine.session_factors(pipe.text_encoder, layers, hparams.rewrite_module_tmp, lam, e,
+                                                      {l: c for l, (_, _, c) in zip(layers, stats)}, dev)
+            shared, info = (fac, [c for _, _, c in stats]), fac.info
+        else:
+            shared = None
+        flags = torch.cat([d.to(torch.int32) for d in differs] + [info])
+        host = torch.empty(flags.shape, dtype=torch.int32, pin_memory=True)
+        host.copy_(flags, non_blocking=True)
+        torch.cuda.current_stream(dev).synchronize()        # the ONE synchronising read
+        host = host.tolist()
+        for i, (n, *_ ) in enumerate(prints["encoder"]):
+            if host[i]:
+                raise ValueError(f"the session was saved on another text encoder: the contents of parameter {n!r} differ from the "
+                                 f"fingerprint in {path}; the encoder's weights are as they were")
+        for i, (n, f, *_ ) in enumerate(prints["statistics"] or ()):
+            if host[len(others) + i]:
+                raise ValueError(f"layer {n}: the statistics of {stats[i][1]} are not the ones the session's rows were computed "
+                                 f"under (saved from {f}); the encoder's weights are as they were")
+        if weights == "check":
+            at = len(words)
+            for i, l in enumerate(layers):
+                if host[at + i]:
+                    raise ValueError(f"{hparams.rewrite_module_tmp.format(l)}.weight differs from the edited weight in {path}: load "
+                                     f"the saved weights first (load_edited_weights, or weights='load')")
+        if host[-1] != 0:
+            raise torch.linalg.LinAlgError(
+                f"load of {path}: " + (f"the folded system of {counters['folded']} rows" if private is not None else "lam C'") +
+                f" is not positive definite (non-positive pivot at column {host[-1] - 1}); no session was made and the encoder's "
+                f"weights are as they were")
+        if commit is not None:
+            commit()
+        # sound: the state moves in
+        if M > 0:
+            sess.keys = hip.PreservedKeys(len(layers), sess.d, sess.capacity, dev)
+            sess.keys.load_state_dict(state["keys"])
+        sess.steps, sess.folds, sess.folded = counters["steps"], counters["folds"], counters["folded"]
+        sess.retained, sess.released, sess._retains = counters["retained"], counters["released"], counters["retains"]
+        sess._ledger = [tuple(r) for r in state["ledger"]]
+        sess._folded_sources = set(state["folded_sources"])
+        sess._archive_ledger = [tuple(r) for r in state["archive_ledger"]]
+        sess._shared, sess.private_factors, sess._base = shared, private, base
+        if state["archive"] is not None:
+            sess._archived = counters["folded"]
+            sess._archive = [a[:sess._archived].to(dev) for a in state["archive"]]
+        if state["orig"] is not None:
+            sess._orig = {l: state["orig"][i].to(dev) for i, l in enumerate(layers)}
+        if weights == "load":
+            with torch.no_grad():
+                for i, l in enumerate(layers):
+                    live[l].copy_(state["weights"][i])
+        LP = clip_forward.LAST_PATHS
+        LP["session_steps"], LP["session_preserved_rows"], LP["session_loaded_rows"] = sess.steps, M, M
+        LP["session_folds"], LP["session_folded_rows"] = sess.folds, sess.folded
+        LP["session_retained_rows"], LP["session_released_rows"] = sess.retained, sess.released
+        if verbose:
+            print(f"Session loaded from {path}: {M} preserved and {sess.folded} folded rows after {sess.steps} steps")
+        return sess
 
 
 def sweep_emcid_text_encoder(pipe, requests: List[Dict], hparams: EMCIDHyperParams, grid, device: Optional[str] = None,

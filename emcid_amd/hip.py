@@ -20,7 +20,7 @@ _lib = None
 EXPORTS = [
     "emcid_abi_version", "emcid_last_error", "emcid_gram_accumulate_f32", "emcid_symmetrize_lower_f32",
     "emcid_gather_mean_f32", "emcid_edit_workspace_bytes", "emcid_edit_layer_f64", "emcid_assemble_spd_f64",
-    "emcid_cholesky_f64", "emcid_cholesky_solve_f64", "emcid_delta_w_f64", "emcid_dgemm_f64", "emcid_dgemm_ex_f64", "emcid_dgemm_batched_f64", "emcid_streamk_workspace_bytes", "emcid_dgemm_streamk_f64", "emcid_debug_streamk_stamps", "emcid_debug_step_stamps", "emcid_debug_linear_sp16_stamps", "emcid_fingerprint_store", "emcid_fingerprint_check", "emcid_axpy_f32",
+    "emcid_cholesky_f64", "emcid_cholesky_solve_f64", "emcid_delta_w_f64", "emcid_dgemm_f64", "emcid_dgemm_ex_f64", "emcid_dgemm_batched_f64", "emcid_streamk_workspace_bytes", "emcid_dgemm_streamk_f64", "emcid_debug_streamk_stamps", "emcid_debug_step_stamps", "emcid_debug_linear_sp16_stamps", "emcid_fingerprint_store", "emcid_fingerprint_check", "emcid_fingerprint_content", "emcid_axpy_f32",
     "emcid_profile_enable", "emcid_profile_collect", "emcid_attention_f32", "emcid_edit_layer_shard_f64",
     "emcid_apply_update_f32", "emcid_inverse_workspace_doubles", "emcid_quick_gelu_f32", "emcid_add_layernorm_f32", "emcid_embed_layernorm_f32", "emcid_tree_attention_f32", "emcid_debug_leaf_stamps",
     "emcid_cov_factor_workspace_bytes", "emcid_factor_cov_f64", "emcid_cov_inverse_f64", "emcid_cov_factor_rescale_f64",
@@ -123,6 +123,7 @@ def load():
         "emcid_debug_linear_sp16_stamps": (i32, [p]),
         "emcid_fingerprint_store": (i32, [i64, p, p, p, p, i64, p]),
         "emcid_fingerprint_check": (i32, [p, i64, i64, i64, p, p, p]),
+        "emcid_fingerprint_content": (i32, [i64, p, p, p, p]),
         "emcid_debug_step_stamps": (i32, [p]),
         "emcid_dgemm_streamk_f64": (i32, [i32, i64, i64, i64, f64, p, i64, p, i64, p, i64, i32, i32, f64, p, i64, p]),
         "emcid_axpy_f32": (i32, [p, p, i64, p]),
@@ -463,6 +464,37 @@ def fingerprint_check(table: torch.Tensor, first_slot: int, n_slots: int, flag: 
         mask[k >> 6] |= 1 << (k & 63)
     _check(load().emcid_fingerprint_check(_ptr(table, torch.int64, "table"), table.shape[0], int(first_slot), int(n_slots), mask,
                                           _ptr(flag, torch.int32, "flag"), _stream(table)), "emcid_fingerprint_check")
+
+
+def fingerprint_content(tensors) -> torch.Tensor:
+    """The guard's fingerprint of the BYTES of every tensor of ``tensors`` (all in HBM, on one device) without its address
+    (include/emcid_hip.h, "content fingerprint"): an int64 tensor of len(tensors) words on that device — one launch per 32
+    tensors on the current stream, no synchronisation; equal bytes give equal words in any process.  A tensor whose size is no
+    multiple of 16 bytes (or that is not contiguous, or not 16-byte aligned) is fingerprinted as a contiguous copy padded with
+    zeros.  A word says nothing of the shape or dtype: compare those on the host."""
+    tensors = list(tensors)
+    if not tensors:
+        raise EmcidHipError("fingerprint_content needs at least one tensor")
+    dev = tensors[0].device
+    held = []
+    for k, t in enumerate(tensors):
+        if not t.is_cuda or t.device != dev:
+            raise EmcidHipError(f"fingerprint_content: tensor {k} must live in HBM on {dev} (got {t.device}); there is no CPU path")
+        t = t.detach()
+        nbytes = t.numel() * t.element_size()
+        if nbytes == 0:
+            raise EmcidHipError(f"fingerprint_content: tensor {k} is empty")
+        if nbytes % 16 or t.data_ptr() % 16 or not t.is_contiguous():
+            padded = torch.zeros((nbytes + 15) // 16 * 16, dtype=torch.uint8, device=dev)
+            padded[:nbytes].view(t.dtype).copy_(t.reshape(-1))
+            t = padded
+        held.append(t)
+    n = len(held)
+    out = torch.zeros(n, dtype=torch.int64, device=dev)
+    ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in held])
+    sizes = (C.c_int64 * n)(*[t.numel() * t.element_size() for t in held])
+    _check(load().emcid_fingerprint_content(n, ptrs, sizes, _ptr(out, torch.int64, "out"), _stream(out)), "emcid_fingerprint_content")
+    return out
 
 
 def axpy_(W: torch.Tensor, dW: torch.Tensor):
@@ -1245,6 +1277,41 @@ def edit_layer_dual_apply(K, Zc, zs_t, factors: CovFactors, layer_index: int, ed
     return {"dW": dW, "ws": ws}
 
 
+def check_preserved_state(sd, n_layers: int, d: int, capacity: int) -> int:
+    """Would a state of ``n_layers`` layers of width ``d`` at ``capacity`` take ``sd`` (a ``PreservedKeys.state_dict()``)?  Returns
+    its M; ``EmcidHipError`` otherwise, naming what does not fit.  Pure host code: only shapes and dtypes are looked at."""
+    def bad(what):
+        return EmcidHipError(f"preserved key state: {what}")
+
+    if not isinstance(sd, dict):
+        raise bad(f"a dict is expected (got {type(sd).__name__})")
+    missing = [k for k in ("M", "d", "n_layers", "Yp", "Lp", "tile_inv", "row_scale") if k not in sd]
+    if missing:
+        raise bad(f"no entry {missing}")
+    M = sd["M"]
+    if isinstance(M, bool) or not isinstance(M, int) or M < 0:
+        raise bad(f"M must be a non-negative integer (got {M!r})")
+    if sd["d"] != d:
+        raise bad(f"its rows are of width d = {sd['d']}, this state's of d = {d}")
+    if sd["n_layers"] != n_layers:
+        raise bad(f"it holds {sd['n_layers']} layers, this state {n_layers}")
+    if M > capacity:
+        raise bad(f"its M = {M} committed rows exceed this state's capacity {capacity}")
+    tiles = (M + NB - 1) // NB
+    for name, shape in (("Yp", (M, d)), ("Lp", (M, M)), ("tile_inv", (tiles, NB, NB))):
+        ts = sd[name]
+        if not isinstance(ts, (list, tuple)) or len(ts) != n_layers:
+            raise bad(f"{name} must be a list of {n_layers} tensors")
+        for i, t in enumerate(ts):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != shape:
+                got = (tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__
+                raise bad(f"{name}[{i}] must be an f64 tensor of {shape} for M = {M}, d = {d} (got {got})")
+    rs = sd["row_scale"]
+    if not isinstance(rs, torch.Tensor) or rs.dtype != torch.float64 or tuple(rs.shape) != (M,):
+        raise bad(f"row_scale must be an f64 tensor of ({M},)")
+    return M
+
+
 class PreservedKeys:
     """The session state of the dual solver for ``n_layers`` edited layers (include/emcid_hip.h, "PRESERVED key set"): per layer
     Yp (capacity, dp), Lp (capacity, capacity) and the inverses of Lp's diagonal 128-tiles, f64 in HBM, allocated once —
@@ -1280,6 +1347,55 @@ class PreservedKeys:
 
     def reset(self):
         self.M = 0
+
+    def state_dict(self, sync: bool = True) -> dict:
+        """The committed part, on the host, in a form that knows nothing of ``capacity`` (so of ``ldl`` and the tile count): per
+        layer ``Yp`` (M, d) — the padding columns are zero by construction —, ``Lp`` (M, M) and ``tile_inv`` (ceil(M / 128), 128,
+        128), the inverses of the diagonal tiles that rows < M touch, the last one zero outside the rows and columns below M (the
+        leading block of a lower-triangular inverse is the inverse of the leading block); ``row_scale`` (M,); ``M``, ``d``,
+        ``n_layers``.  What ``load_state_dict`` of a state of ANY capacity >= M takes.  The state is not changed.  From HBM the
+        copies go to page-locked memory on the current stream, followed by ONE synchronisation; ``sync=False`` leaves that to
+        the caller (the tensors are not to be read before)."""
+        M, d, tiles = self.M, self.d, (self.M + NB - 1) // NB
+        w = M - NB * (tiles - 1)                    # rows of the last tile that count
+
+        def host(t: torch.Tensor) -> torch.Tensor:
+            if not t.is_cuda:
+                return t.clone()
+            out = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+            out.copy_(t, non_blocking=True)
+            return out
+
+        def tile_part(ti: torch.Tensor) -> torch.Tensor:
+            ti = ti[:tiles].clone()
+            if tiles and w < NB:
+                ti[-1, w:, :] = 0
+                ti[-1, :, w:] = 0
+            return ti
+
+        sd = {"M": M, "d": d, "n_layers": self.n_layers,
+              "Yp": [host(y[:M, :d].contiguous()) for y in self.Yp],
+              "Lp": [host(l[:M, :M].contiguous()) for l in self.Lp],
+              "tile_inv": [host(tile_part(t)) for t in self.tile_inv],
+              "row_scale": self.row_scale[:M].clone()}
+        if sync and self.Yp[0].is_cuda:
+            torch.cuda.current_stream(self.Yp[0].device).synchronize()
+        return sd
+
+    def load_state_dict(self, sd: dict):
+        """Make the rows of ``sd`` (a ``state_dict()``, of a state of any capacity) this state's committed set: checked on the host
+        first (``check_preserved_state``: ``EmcidHipError`` for M > capacity, another d or layer count, a tensor of another shape
+        or dtype — nothing is copied then), then every row and tile is copied to where THIS capacity's layout wants it.  What lies
+        behind row M stays as it is: no entry of the library reads it before writing it."""
+        M = check_preserved_state(sd, self.n_layers, self.d, self.capacity)
+        tiles = (M + NB - 1) // NB
+        for i in range(self.n_layers):
+            self.Yp[i][:M, :self.d].copy_(sd["Yp"][i])
+            self.Yp[i][:M, self.d:].zero_()
+            self.Lp[i][:M, :M].copy_(sd["Lp"][i])
+            self.tile_inv[i][:tiles].copy_(sd["tile_inv"][i])
+        self.row_scale[:M] = sd["row_scale"]
+        self.M = M
 
     def check_layer(self, layer_index: int):
         if not 0 <= layer_index < self.n_layers:
@@ -1540,6 +1656,23 @@ def session_refold_update(factors: CovFactors, state: PreservedKeys, layer_index
         _ptr(factors.buf), factors.n_layers, factors.d, int(layer_index), Yp, ldy, M, state.capacity,
         _ptr(archive, torch.float64, "archive"), archive.stride(0), n_archived, _ptr(rel_idx) if n_rel else None, n_rel,
         _ptr(base_l, torch.float64, "base"), _stream(factors.buf)), "emcid_session_refold_update_f64")
+
+
+def cov_factor_from_base(base: torch.Tensor, d: int, lam: float, edit_weight: float) -> CovFactors:
+    """A new workspace, its caller's own, holding the factors of the systems ``base`` (n_layers, dp, dp) f64 holds in its lower
+    triangles (a folded session's accumulator, ``cov_factor_fold``): every layer's system is copied into its M region, made
+    symmetric from the lower triangle, and all of them are factored and inverted as the one batched chain of a release across a
+    fold (``cov_factor_refactor``).  Asynchronous on the current stream; ``info`` of the result reports a non-positive pivot;
+    ``base`` is only read."""
+    n_layers = int(base.shape[0])
+    fac = CovFactors(n_layers, int(d), base.device)
+    if base.dtype != torch.float64 or tuple(base.shape) != (n_layers, fac.dp, fac.dp):
+        raise EmcidHipError(f"base must be an f64 tensor of {n_layers} x {fac.dp} x {fac.dp} (got {tuple(base.shape)}, {base.dtype})")
+    regions = fac.buf[:n_layers * fac.dp * fac.dp].view(n_layers, fac.dp, fac.dp)
+    torch.tril(base, out=regions)
+    regions += torch.tril(base, -1).transpose(1, 2)
+    fac.lam, fac.edit_weight = float(lam), float(edit_weight)
+    return cov_factor_refactor(fac)
 
 
 def cov_factor_refactor(factors: CovFactors) -> CovFactors:

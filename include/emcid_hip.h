@@ -197,6 +197,16 @@ int emcid_fingerprint_store(int64_t n, const void* const* data, const int64_t* b
 int emcid_fingerprint_check(const void* table, int64_t table_slots, int64_t first_slot, int64_t n_slots, const uint64_t* skip_mask,
                             int* flag, void* stream);
 
+/* Content fingerprint (entry point added under ABI 16; edit sessions saved to a file and resumed in another process).  A table
+ * entry of the guard above carries the tensor's address, which means nothing in another process: this entry writes
+ * out_dev[i] = the fingerprint word emcid_fingerprint_store computes for the bytes of tensor i, and nothing else — equal bytes at
+ * two addresses give equal words.  Host arrays of n pointers / sizes, out_dev [n] in HBM; one launch per 32 tensors, one
+ * workgroup per tensor, no synchronisation.  bytes % 16 == 0 and 16-byte aligned pointers, as above (a caller with another size
+ * pads a copy with zeros: hip.fingerprint_content); a refused call has launched nothing.  The sampling is the guard's: a tensor
+ * of more than 64 KB is read at 4 096 evenly spaced vectors, so the word detects another file or another checkpoint, not every
+ * single-element change of a large tensor. */
+int emcid_fingerprint_content(int64_t n, const void* const* data, const int64_t* bytes, uint64_t* out_dev, void* stream);
+
 /* ---- native layer runner of the trie forward (csrc/clip_layers.hip) ---------------------------------------------------------------
  * One C call issues all launches of a run of CLIP text-encoder layers on the split-fp16 projections (the forward the reference
  * gets from CLIPTextModel.forward, emcid/compute_z.py:2296-2316, inside the layer loop of emcid/emcid_main.py:981-1073): the same
