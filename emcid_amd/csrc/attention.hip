@@ -382,7 +382,8 @@ extern "C" int emcid_tree_attention_f32(const float* q, int64_t ldq, const float
 
 // y = a + b ; z = LayerNorm(y) * gamma + beta   (one row per workgroup, the row lives in registers between the passes).
 // The residual add and the LayerNorm that follows it in every transformer block, as one pass over HBM instead of two
-// kernels (add: 2 reads + 1 write; layer norm: 1 read + 1 write).  Two-pass mean / variance like torch's.
+// kernels (add: 2 reads + 1 write; layer norm: 1 read + 1 write).  Two-pass mean / variance, the mean corrected by the sum of
+// the centred values (add_layernorm_wave_kernel says why).
 constexpr int LN_MAX_V4 = 8;    // float4 chunks per thread: rows up to 8 * 256 * 4 = 8192 columns
 __global__ __launch_bounds__(256) void add_layernorm_f32_kernel(const float* __restrict__ a, int64_t lda, const float* __restrict__ b,
                                                                  int64_t ldb, const float* __restrict__ gamma,
@@ -415,16 +416,19 @@ __global__ __launch_bounds__(256) void add_layernorm_f32_kernel(const float* __r
         return (red[0] + red[1]) + (red[2] + red[3]);
     };
     const float mean = block_sum(sum) / (float)cols;
-    float sq = 0.f;
+    float sq = 0.f, s1 = 0.f;
 #pragma unroll
     for (int i = 0; i < LN_MAX_V4; ++i) {
         const int c = threadIdx.x + i * 256;
         if (c < nv) {
             const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
+            s1 += (dx + dy) + (dz + dw);
             sq += (dx * dx + dy * dy) + (dz * dz + dw * dw);
         }
     }
-    const float rstd = rsqrtf(block_sum(sq) / (float)cols + eps);
+    // what the fp32 sum lost of the mean (see add_layernorm_wave_kernel): the row is centred at mean + corr
+    const float corr = block_sum(s1) / (float)cols;
+    const float rstd = rsqrtf(fmaxf(block_sum(sq) / (float)cols - corr * corr, 0.f) + eps);
     float4* py = reinterpret_cast<float4*>(y + row * (int64_t)cols);
     float4* pz = reinterpret_cast<float4*>(z + row * (int64_t)cols);
     const float4* pg = reinterpret_cast<const float4*>(gamma);
@@ -435,8 +439,8 @@ __global__ __launch_bounds__(256) void add_layernorm_f32_kernel(const float* __r
         if (c < nv) {
             const float4 g = pg[c], e = pe[c];
             if (y) py[c] = v[i];
-            pz[c] = make_float4((v[i].x - mean) * rstd * g.x + e.x, (v[i].y - mean) * rstd * g.y + e.y,
-                                (v[i].z - mean) * rstd * g.z + e.z, (v[i].w - mean) * rstd * g.w + e.w);
+            pz[c] = make_float4(((v[i].x - mean) - corr) * rstd * g.x + e.x, ((v[i].y - mean) - corr) * rstd * g.y + e.y,
+                                ((v[i].z - mean) - corr) * rstd * g.z + e.z, ((v[i].w - mean) - corr) * rstd * g.w + e.w);
         }
     }
 }
@@ -477,18 +481,29 @@ __global__ __launch_bounds__(256) void add_layernorm_wave_kernel(const float* __
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
     const float mean = sum / (float)cols;
-    float sq = 0.f;
+    // On a row whose mean dwarfs its spread (a residual stream riding on an offset of 500) the fp32 sum above is good to a few
+    // ulp of cols * |mean| only, and that error, divided by the spread, is the error of every output.  The differences v - mean
+    // are exact to the spread's own precision, so their sum gives back what the first sum lost: the row is centred at
+    // mean + corr (applied as (v - mean) - corr: mean + corr itself would round corr away again), and
+    // sum (d - corr)^2 = sum d^2 - cols corr^2 (clamped at zero: on a constant row the two terms are equal up to rounding).
+    // Both sums share the pass and the shuffles.
+    float sq = 0.f, s1 = 0.f;
 #pragma unroll
     for (int i = 0; i < LN_MAX_V4; ++i) {
         const int c = lane + i * 64;
         if (c < nv) {
             const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
+            s1 += (dx + dy) + (dz + dw);
             sq += (dx * dx + dy * dy) + (dz * dz + dw * dw);
         }
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
-    const float rstd = rsqrtf(sq / (float)cols + eps);
+    for (int o = 32; o > 0; o >>= 1) {
+        s1 += __shfl_xor(s1, o, 64);
+        sq += __shfl_xor(sq, o, 64);
+    }
+    const float corr = s1 / (float)cols;
+    const float rstd = rsqrtf(fmaxf(sq / (float)cols - corr * corr, 0.f) + eps);
     float4* py = reinterpret_cast<float4*>(y + row * (int64_t)cols);
     float4* pz = reinterpret_cast<float4*>(z + row * (int64_t)cols);
     const float4* pg = reinterpret_cast<const float4*>(gamma);
@@ -500,8 +515,8 @@ __global__ __launch_bounds__(256) void add_layernorm_wave_kernel(const float* __
         if (c < nv) {
             const float4 g = pg[c], e = pe[c];
             if (y) py[c] = v[i];
-            v[i] = make_float4((v[i].x - mean) * rstd * g.x + e.x, (v[i].y - mean) * rstd * g.y + e.y,
-                               (v[i].z - mean) * rstd * g.z + e.z, (v[i].w - mean) * rstd * g.w + e.w);
+            v[i] = make_float4(((v[i].x - mean) - corr) * rstd * g.x + e.x, ((v[i].y - mean) - corr) * rstd * g.y + e.y,
+                               ((v[i].z - mean) - corr) * rstd * g.z + e.z, ((v[i].w - mean) - corr) * rstd * g.w + e.w);
             if (z) pz[c] = v[i];
             amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v[i].x), fabsf(v[i].y))), fmaxf(fabsf(v[i].z), fabsf(v[i].w)));
             ss += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
