@@ -1571,9 +1571,266 @@ class EditSession:
         return sess
 
 
+# ---- edit scores: did the edit take, and what did it move --------------------------------------------------------------------
+
+def _median(x: torch.Tensor) -> float:
+    """The median of a vector: of an even number of values, the mean of the middle two (``torch.median`` takes the lower one)."""
+    return float(torch.quantile(x.double(), 0.5))
+
+
+class EditScore:
+    """What ``EditScorer.score`` read, as fp64 tensors on the host.
+
+    Per concept row, in the order of ``EditSession.rows()`` (request by request, its num_edit_tokens rows in turn):
+        sources   [(request["source"], token index)]
+        left      ||v* - Z|| / ||v* - Z0||: the fraction of the way to the target that is still to go (1: nothing moved, 0: on target)
+        cos       cos(Z - Z0, v* - Z0): whether what moved went towards the target (0 where nothing moved)
+        resid, resid0   the two norms ``left`` is the ratio of
+    Per holdout prompt, in the order given:
+        holdout     the prompt strings
+        drift_max, drift_mean   max and mean over the prompt's tokens BOS ... EOS of ||f - f0|| / ||f0||, f the encoder's output
+                    (final LayerNorm applied) at the token, f0 the same before the edit
+        drift_eos   that ratio at the EOS token
+        drift_argmax    the token position of the max (the first one on a tie)"""
+
+    def __init__(self, sources, left, cos, resid, resid0, holdout, drift_max, drift_mean, drift_eos, drift_argmax):
+        self.sources, self.left, self.cos, self.resid, self.resid0 = list(sources), left, cos, resid, resid0
+        self.holdout, self.drift_max, self.drift_mean, self.drift_eos = list(holdout), drift_max, drift_mean, drift_eos
+        self.drift_argmax = drift_argmax
+
+    def summary(self) -> Dict[str, float]:
+        return {"left_median": _median(self.left), "left_max": float(self.left.max()),
+                "drift_max": float(self.drift_max.max()), "drift_median": _median(self.drift_max)}
+
+    def __repr__(self):
+        return "EditScore(" + ", ".join(f"{k}={v:.4g}" for k, v in self.summary().items()) + ")"
+
+
+def score_row_sources(requests: Sequence[Dict], num_edit_tokens: int = 1) -> List[tuple]:
+    """[(source, token index)] in the row order of an edit's concept stack: row rq * k + num (the reference's "rq num")."""
+    k = int(num_edit_tokens)
+    return [(r["source"], num) for r in requests for num in range(k)]
+
+
+SCORE_MAX_CHAIN = 128       # nodes per holdout chain the readout takes (csrc/score.hip; the trie forward's own limit too)
+
+
+def holdout_tokens(tokenizer, prompts: Sequence[str], n_positions: Optional[int] = None):
+    """Generic prompts tokenized for the holdout trie, host only: ((B, S) int64 ids, (B,) int64 EOS positions).  A chain BOS ... EOS
+    longer than ``SCORE_MAX_CHAIN`` nodes, or than the encoder's ``n_positions`` position embeddings, is refused here."""
+    from .compute_z import tokenize_lists
+    prompts = list(prompts)
+    if not prompts or not all(isinstance(p, str) for p in prompts):
+        raise ValueError("holdout must be a non-empty list of prompt strings")
+    enc = tokenize_lists(tokenizer, prompts)
+    ids, mask = np.asarray(enc["input_ids"], dtype=np.int64), np.asarray(enc["attention_mask"], dtype=np.int64)
+    eos = mask.sum(axis=1) - 1
+    if int(eos.min()) < 0:
+        raise ValueError("a holdout prompt tokenizes to nothing")
+    longest = int(eos.max()) + 1
+    if longest > SCORE_MAX_CHAIN:
+        raise clip_forward.UnsupportedEncoder(f"a holdout prompt has {longest} tokens: the score's readout takes chains of up to "
+                                              f"{SCORE_MAX_CHAIN} nodes")
+    if n_positions is not None and longest > int(n_positions):
+        raise ValueError(f"a holdout prompt has {longest} tokens for {int(n_positions)} position embeddings")
+    return ids, eos
+
+
+def holdout_trie(tokenizer, prompts: Sequence[str], device, n_positions: Optional[int] = None):
+    """The prefix trie of generic prompts whose lookup is each prompt's EOS, so that every chain runs BOS ... EOS: (TokenTrie,
+    (B,) int64 EOS positions on the host).  ``trie.lookup_node[p]`` is prompt p's end node; its chain is
+    ``trie.anc[end, 0 .. trie.depth[end]]``."""
+    ids, eos = holdout_tokens(tokenizer, prompts, n_positions)
+    return clip_forward.build_trie(ids, eos, device), eos
+
+
+def select_point(scores: Sequence[EditScore], max_drift: float) -> Optional[int]:
+    """The index of the score with the smallest median ``left`` among those whose largest ``drift_max`` is within ``max_drift``
+    (the first of equals), or None when there is none.  Host only."""
+    best, best_left = None, None
+    for i, s in enumerate(scores):
+        if not float(s.drift_max.max()) <= float(max_drift):
+            continue
+        m = _median(s.left)
+        if best is None or m < best_left:
+            best, best_left = i, m
+    return best
+
+
+class EditScorer:
+    """Scores edits of ONE text encoder by the encoder's own output, on the device.
+
+        scorer = EditScorer(pipe, requests, hparams, device, holdout=[prompt strings], cache_name=...)    # on the BASELINE weights
+        ... any edit of the fc2 weights of hparams.layers: a plain call, a session step, a sweep point ...
+        s = scorer.score()                                                                               # -> EditScore
+
+    Efficacy is read where the closed form acts: Z is the mean over a concept's prompts of the LAST edited layer's fc2 output (bias
+    included) at the lookup rows — the engine's Zc of that layer —, Z0 the same on the baseline weights, and
+    ``left = ||v* - Z|| / ||v* - Z0||``, ``cos = cos(Z - Z0, v* - Z0)`` per concept row.  (The reference takes its residual
+    against this very quantity, emcid_main.py:1002-1016; the residual stream at that layer carries the attention branch and the
+    skip path as well, which the edit does not steer.)  Drift is read where the UNet is conditioned: with H the residual stream
+    after the last encoder layer at every token of every holdout prompt and f = final_layer_norm(H), the ratio
+    ``||f - f0|| / ||f0||`` per token, reduced per prompt to its max, mean and EOS value (``EditScore``).  Positions behind a
+    prompt's EOS — the padding a pipeline feeds the UNet too — are not scored.
+
+    The constructor tokenizes ``requests`` like a plain call (same trie, same lookups, for num_edit_tokens = k > 1 the same leaves
+    and (request, num) rows), reads their v* rows with the call's loader (a missing file is an error: Stage 1 never runs here),
+    builds a second trie over ``holdout`` whose lookups are the prompts' EOS tokens, runs the unedited leading layers on both
+    (``clip_forward.run_prefix``) and keeps the two states, then runs the rest once and keeps Z0 (N k, h) and H0 (holdout nodes, h),
+    raw.  State held: the two entering states, Z0, H0, v*, fp32 in HBM.
+
+    ``score()`` replays layers[0] ... from the two kept states (``run_layers_from`` only reads them): the request trie to
+    layers[-1], the holdout trie to the last layer on every node; Z by the engine's own gather; then TWO launches
+    (``hip.score_rows`` on (Z, Z0, v*) and, behind the final LayerNorm in fp64, on (H, H0); ``hip.score_chains`` over the holdout
+    chains) and ONE pinned readback, the only host synchronisation.  Everything is issued eagerly on the current stream; no weight
+    is moved and every parameter is bit-identical afterwards; the forward's weight-derived caches refresh themselves as in any
+    forward.  Two calls in a row return the same bits.
+
+    Refused before anything is launched: an encoder the prefix-trie forward does not take (``clip_forward.UnsupportedEncoder``,
+    as ``edit_engine.run_sweep``: not HF CLIP, not fp32 in HBM, no final LayerNorm the readout takes, a holdout prompt of more than
+    ``SCORE_MAX_CHAIN`` = 128 tokens); a holdout prompt longer than the position table (``ValueError``); the SDXL pair, a
+    cross-attention ``rewrite_module_tmp``, a collective ``ConceptShard`` (``ValueError``); and a ``score()`` when a parameter other
+    than the edited fc2 weights is not the tensor, at the address, with the in-place version counter it had at construction
+    (``ValueError``: the kept states would no longer be this encoder's).  That check is host-only: a write through ``.data`` or a
+    raw pointer to such a parameter is not seen and is the caller's responsibility.  Not done here: SDXL, sharded calls, scoring
+    on the hooked-HF forward, positions behind the EOS."""
+
+    def __init__(self, pipe, requests: List[Dict], hparams: EMCIDHyperParams, device: Optional[str] = None, holdout=None,
+                 cache_name: Optional[str] = None, shard=None, _plan: Optional[EncoderEditPlan] = None):
+        if isinstance(hparams, EMCIDXLHyperParams) or getattr(pipe, "text_encoder_2", None) is not None:
+            raise ValueError("EditScorer scores one CLIP text encoder: the SDXL pair (EMCIDXLHyperParams / text_encoder_2) is not supported")
+        if not isinstance(hparams, EMCIDHyperParams):
+            raise TypeError(f"hparams must be EMCIDHyperParams, got {type(hparams).__name__}")
+        if _shard_from_env(shard).collective:
+            raise ValueError("EditScorer runs on one rank: a collective ConceptShard is not supported")
+        if len(requests) == 0:
+            raise ValueError("EditScorer needs at least one request")
+        layers = list(hparams.layers)
+        if not layers or sorted(layers) != layers:
+            raise ValueError(f"hparams.layers must be a non-empty list in forward order (got {hparams.layers})")
+        te, tok = pipe.text_encoder, pipe.tokenizer
+        try:
+            weights = [nethook.get_parameter(te, f"{hparams.rewrite_module_tmp.format(l)}.weight") for l in layers]
+        except LookupError as e:
+            raise ValueError(f"EditScorer scores edits of the text encoder's MLP projections; {hparams.rewrite_module_tmp!r} names no "
+                             f"weight of pipe.text_encoder (cross-attention edits are not supported): {e}") from e
+        w = weights[0]
+        if device is not None and torch.device(device).type != w.device.type:
+            raise ValueError(f"device {device!r} but the text encoder's weights live on {w.device}")
+        holdout = list(holdout) if holdout is not None else []
+        if not holdout or not all(isinstance(p, str) for p in holdout):
+            raise ValueError("holdout must be a non-empty list of prompt strings")
+        layer_tmp = getattr(hparams, "layer_module_tmp", None)
+        if layer_tmp is None:
+            raise clip_forward.UnsupportedEncoder("hparams.layer_module_tmp is not set: no prefix-trie forward")
+        if not (w.is_cuda and w.dtype == torch.float32):
+            raise clip_forward.UnsupportedEncoder(f"the prefix-trie forward runs fp32 in HBM (got {w.dtype} on {w.device})")
+        try:
+            graph = clip_forward.discover_cached(te, layer_tmp)
+            if any(graph.layers[l].fc2.weight is not wl for l, wl in zip(layers, weights)):
+                raise clip_forward.UnsupportedEncoder("rewrite_module_tmp is not the layer's mlp.fc2")
+        except (IndexError, LookupError) as e:
+            raise clip_forward.UnsupportedEncoder(str(e)) from e
+        ln = graph.final_layer_norm
+        h = int(w.shape[0])
+        if not (isinstance(ln, torch.nn.LayerNorm) and ln.weight is not None and ln.bias is not None and ln.weight.is_cuda
+                and ln.weight.dtype == torch.float32 and tuple(ln.normalized_shape) == (h,) and h % 4 == 0 and h <= hip.SCORE_MAX_COLS):
+            raise clip_forward.UnsupportedEncoder(f"the score's readout takes an affine fp32 final LayerNorm over h = {h} columns "
+                                                  f"(h % 4 == 0, h <= {hip.SCORE_MAX_COLS})")
+        # (host only: a holdout chain the readout or the position table cannot take is refused before anything is launched)
+        ids_h, eos_h = holdout_tokens(tok, holdout, graph.position_embedding.num_embeddings)
+        if _plan is None and _any_vstar_missing(requests, hparams, cache_name, ""):
+            raise FileNotFoundError(f"a v* file of the {len(requests)} requests is missing under {cache_name!r}: an EditScorer reads "
+                                    f"the targets an edit was made towards and never runs Stage 1")
+        k = int(getattr(hparams, "num_edit_tokens", 1) or 1)
+        self.pipe, self.hparams, self.layers, self.graph, self.k = pipe, hparams, layers, graph, k
+        self.sources, self.holdout = score_row_sources(requests, k), holdout
+        dev = w.device
+        # ``_plan`` (sweep_emcid_text_encoder): the sweep's own prepared plan of these very requests — its trie, its v* rows (read,
+        # or computed by Stage 1, the way a call does) and the state its prefix run left, which the sweep's points replay as well
+        plan = _plan if _plan is not None else prepare_encoder_edit(
+            te, tok, requests, layers, hparams.rewrite_module_tmp, float(hparams.mom2_update_weight), float(hparams.edit_weight),
+            lambda: load_v_stars(requests, hparams, cache_name, "", None, width=h, pin=True),
+            lambda: {}, ConceptShard(), layer_module_tmp=layer_tmp, num_edit_tokens=k)
+        if plan.chunk is None or plan.graph is not graph or plan.chunk.state is None or plan.chunk.state[0] != layers[0] \
+                or plan.layers != layers or plan.num_edit_tokens != k:
+            raise clip_forward.UnsupportedEncoder("the requests did not take the prefix-trie forward")
+        self.chunk, self.zs = plan.chunk, plan.resolve_targets()
+        self._state = tuple(plan.chunk.state[1:])
+        if _plan is None:
+            plan.chunk.state = None
+        with torch.no_grad():
+            self.trie_h, self.eos = clip_forward.build_trie(ids_h, eos_h, dev), eos_h
+            self._state_h = tuple(clip_forward.run_prefix(graph, self.trie_h, layers[0]))
+            self._frozen = self._signature()
+            Z0, H0 = self._forward()
+        self.Z0, self.H0 = Z0.clone(), H0
+        n, B = self.Z0.shape[0], len(holdout)
+        if n != len(self.sources) or tuple(self.zs.shape) != tuple(self.Z0.shape):
+            raise ValueError(f"{n} concept rows for {len(self.sources)} (source, token) pairs and v* of shape {tuple(self.zs.shape)}")
+        self._out = torch.empty(n * 8 + B * 4, dtype=torch.float64, device=dev)
+        self._node = torch.empty(H0.shape[0], 8, dtype=torch.float64, device=dev)
+        self._host = torch.empty(n * 8 + B * 4, dtype=torch.float64, pin_memory=True)
+
+    def _signature(self):
+        """(name, identity, address, in-place version) of every parameter but the edited fc2 weights — of those: identity alone."""
+        edited = {id(self.graph.layers[l].fc2.weight) for l in self.layers}
+        return tuple((n, id(p)) if id(p) in edited else (n, id(p), p.data_ptr(), p._version)
+                     for n, p in self.pipe.text_encoder.named_parameters())
+
+    def _forward(self):
+        """(Z (N k, h), H (holdout nodes, h)) fp32 on the weights as they are: the replay from the two kept states."""
+        g, ch, first, last = self.graph, self.chunk, self.layers[0], self.layers[-1]
+        box = []
+
+        def on_fc2(li, x, out, mid=None, next_ln=None):
+            # the engine's own Zc of its last layer: fc2 is affine, so the mean output at the lookup rows is fc2 of the mean key
+            if li != last:
+                return out
+            layer = g.layers[li]
+            xf = x.float() if isinstance(x, hip.SplitRows) else x
+            K = hip.gather_mean(xf.unsqueeze(0).expand(ch.lookup_query.numel(), -1, -1), ch.lookup_query, ch.cseg)
+            box.append(clip_forward.linear(K, layer.fc2.weight, layer.fc2.bias, wsp=layer.split_of("fc2")))
+            return None
+
+        clip_forward.run_layers_from(g, ch.trie, self._state, first, last, on_fc2, fc2_by_callback=(last,), edit_callback=True)
+        H = clip_forward.run_layers_from(g, self.trie_h, self._state_h, first, len(g.layers) - 1, None, last_rows_only=False)[0]
+        if g.guard is not None:
+            g.guard.flush()          # (fingerprints of the weights that cache entries were made from in this replay, if any)
+        clip_forward.LAST_PATHS["score_replays"] = clip_forward.LAST_PATHS.get("score_replays", 0) + 1
+        return box[0], H
+
+    def score(self) -> EditScore:
+        """Score the weights as they are against the baseline of construction (class docstring): one replay, two launches, one
+        pinned readback."""
+        if self._signature() != self._frozen:
+            now = dict((s[0], s) for s in self._signature())
+            moved = [s[0] for s in self._frozen if now.get(s[0]) != s]
+            raise ValueError(f"parameters other than the edited fc2 weights changed since this EditScorer was built "
+                             f"({', '.join(moved[:4]) or 'the parameter list'}{', ...' if len(moved) > 4 else ''}): its kept states "
+                             f"are no longer this encoder's; build a new EditScorer")
+        n, B = self.Z0.shape[0], len(self.holdout)
+        with torch.no_grad():
+            Z, H = self._forward()
+            hip.score_rows(Z, self.Z0, t=self.zs, out=self._out[:n * 8].view(n, 8))
+            hip.score_rows(H, self.H0, ln=self.graph.final_layer_norm, out=self._node)
+            hip.score_chains(self._node, self.trie_h.anc, self.trie_h.depth, self.trie_h.lookup_node,
+                             out=self._out[n * 8:].view(B, 4))
+            self._host.copy_(self._out, non_blocking=True)
+            torch.cuda.current_stream(self._out.device).synchronize()
+        rows, chains = self._host[:n * 8].view(n, 8).clone(), self._host[n * 8:].view(B, 4).clone()
+        moved2, resid2, resid02, dot = rows[:, 0], rows[:, 4], rows[:, 5], rows[:, 6]
+        tiny = torch.finfo(torch.float64).tiny
+        left = torch.where(resid02 > 0, (resid2 / resid02.clamp(min=tiny)).sqrt(), torch.zeros_like(resid2))
+        den = (moved2 * resid02).sqrt()
+        cos = torch.where(den > 0, dot / den.clamp(min=tiny), torch.zeros_like(dot))
+        return EditScore(self.sources, left, cos, resid2.sqrt(), resid02.sqrt(), self.holdout, chains[:, 0].clone(),
+                         chains[:, 1].clone(), chains[:, 2].clone(), chains[:, 3].clone())
+
+
 def sweep_emcid_text_encoder(pipe, requests: List[Dict], hparams: EMCIDHyperParams, grid, device: Optional[str] = None,
                              visit=None, cache_name: Optional[str] = None, stat_dir=STATS_DIR, shard=None, stage1=None,
-                             verbose: bool = False) -> list:
+                             verbose: bool = False, score=None) -> list:
     """One request set at every (mom2_weight, edit_weight) pair of ``grid`` (the reference sets them per run, experiments/
     emcid_test.py:924-930, and walks lists of them, ablation.py::edit_weight_ablation) in ONE call.  For each pair, in order, the
     text encoder holds the weights ``apply_emcid_to_text_encoder(..., mom2_weight=, edit_weight=)`` would have left from the
@@ -1586,7 +1843,15 @@ def sweep_emcid_text_encoder(pipe, requests: List[Dict], hparams: EMCIDHyperPara
     cannot take gets one ordinary call per point (counted by clip_forward.note_fallback).  Invalid grids raise ValueError first.
     When the engine finds a weight rewritten behind the forward's caches (StaleWeightCacheError, see _retry_if_stale) the sweep is
     redone once from its first point: ``visit`` is then called again for points it has already seen, and only the second pass's
-    return values are kept — a ``visit`` with side effects should be idempotent per point."""
+    return values are kept — a ``visit`` with side effects should be idempotent per point.
+
+    ``score=[holdout prompt strings]`` scores every point on the device (``EditScorer``, built once on the original weights before
+    the first point): with ``visit=None`` the result is one ``EditScore`` per point and no weight is copied to the host, with a
+    ``visit`` it is ``(visit(point, pipe), EditScore)`` per point; ``select_point`` picks among them.  The scorer takes the sweep's
+    own prepared plan — the request trie, the state after the unedited leading layers, and the v* rows as the sweep's loader got
+    them (a missing v* file runs Stage 1 as without ``score=``) — so only the holdout prompts are tokenized and run in addition.
+    It needs the prefix-trie forward (``UnsupportedEncoder`` otherwise, raised after the preparation) and one rank (``ValueError``).
+    Without ``score=`` nothing changes."""
     from .edit_engine import run_sweep, validate_grid
     pts = validate_grid(grid)
     hp = deepcopy(hparams)
@@ -1595,7 +1860,17 @@ def sweep_emcid_text_encoder(pipe, requests: List[Dict], hparams: EMCIDHyperPara
         raise ValueError(f"the text encoder is on {next(pipe.text_encoder.parameters()).device}, not on {device}")
     names = [f"{hp.rewrite_module_tmp.format(layer)}.weight" for layer in hp.layers]
 
+    scorer = None
+    if score is not None:       # what a scorer refuses whatever the encoder, before the preparation launches anything
+        if _shard_from_env(shard).collective:
+            raise ValueError("score= runs on one rank: a collective ConceptShard is not supported")
+        score = list(score)
+        if not score or not all(isinstance(p, str) for p in score):
+            raise ValueError("score= takes the holdout: a non-empty list of prompt strings")
+
     def collect(point):
+        if scorer is not None:
+            return scorer.score() if visit is None else (visit(point, pipe), scorer.score())
         if visit is not None:
             return visit(point, pipe)
         return {n: nethook.get_parameter(pipe.text_encoder, n).detach().to("cpu", torch.float32).clone() for n in names}
@@ -1605,7 +1880,13 @@ def sweep_emcid_text_encoder(pipe, requests: List[Dict], hparams: EMCIDHyperPara
         plan = prepare_text_encoder_edit(pipe.text_encoder, pipe.tokenizer, requests, hp, hp.layers, hp.mom2_update_weight,
                                          stat_dir, cache_name, "", verbose, shard, _default_stage1(pipe, hp, stage1))
         if plan.chunk is None or plan.graph is None:
+            if score is not None:
+                raise clip_forward.UnsupportedEncoder("score= needs the prefix-trie forward, which this encoder or request set did not take")
             break
+        if score is not None:
+            # on the sweep's own plan (its trie, v* rows and prefix state: nothing is tokenized or run twice), before the first point,
+            # on the original weights; again after a stale-cache retry, whose new plan belongs to a new graph
+            scorer = EditScorer(pipe, requests, hp, device, holdout=score, cache_name=cache_name, shard=shard, _plan=plan)
         try:
             return run_sweep(plan, pts, lambda index, point: collect(point))
         except clip_forward.StaleWeightCacheError as e:

@@ -33,6 +33,7 @@ EXPORTS = [
     "emcid_session_release_workspace_bytes", "emcid_session_release_f64",
     "emcid_cov_factor_fold_workspace_bytes", "emcid_cov_factor_fold_f64",
     "emcid_session_refold_update_f64", "emcid_cov_factor_refactor_f64",
+    "emcid_score_rows_f32", "emcid_score_chains_f64",
     "emcid_edit_lu_workspace_bytes", "emcid_edit_layer_lu_f64", "emcid_lu_solve_f64",
     "emcid_edit_dual_cols_stage1_f64", "emcid_edit_dual_s", "emcid_edit_dual_u", "emcid_edit_dual_cols_stage2_f64",
     "emcid_apply_update2d_f32", "emcid_linear_f32", "emcid_linear_ws_f32", "emcid_linear_workspace_bytes",
@@ -105,6 +106,8 @@ def load():
         "emcid_cov_factor_fold_f64": (i32, [p, f64, p, i64, i64, i64, p, f64, f64, i32, p, i64, i64, i64, p, p, i64, p, p]),
         "emcid_session_refold_update_f64": (i32, [p, i64, i64, i64, p, i64, i64, i64, p, i64, i64, p, i64, p, p]),
         "emcid_cov_factor_refactor_f64": (i32, [p, i64, i64, i64, p, p]),
+        "emcid_score_rows_f32": (i32, [p, i64, p, i64, p, i64, p, p, f32, i64, i64, p, p]),
+        "emcid_score_chains_f64": (i32, [p, i64, p, i64, p, p, i64, p, p]),
         "emcid_cholesky_solve_f64": (i32, [p, i64, i64, p, p, p, i64, i64, p]),
         "emcid_edit_dual_cols_stage1_f64": (i32, [p, p, p, i64, i64, i64, f64, i32, f64, p, i64, i64, p, i32, p, i64, p]),
         "emcid_edit_dual_s": (p, [p, i64, i64, i64]),
@@ -1578,6 +1581,67 @@ def session_step_norms(ws: PreserveWorkspace, N: int, d: int, h: int, state: Pre
         _ptr(ws.buf), ws.nbytes, N, int(d), int(h), state.capacity, M, _ptr(drift, torch.float64, "drift") if M > 0 else None,
         _ptr(left, torch.float64, "left"), _ptr(resid, torch.float64, "resid"), _stream(ws.buf)), "emcid_session_step_norms_f64")
     return {"drift": drift, "left": left, "resid": resid}
+
+
+# ---- the readout of an edit score (csrc/score.hip) -----------------------------------------------------------------------------
+
+SCORE_MAX_COLS = 2048
+
+
+def score_rows(a: torch.Tensor, b: torch.Tensor, t: Optional[torch.Tensor] = None, ln: Optional[torch.nn.LayerNorm] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(rows, 8) f64 in HBM, one launch (include/emcid_hip.h, emcid_score_rows_f32): per row of the fp32 matrices ``a``, ``b``
+    (rows, cols) — behind ``ln`` (an affine LayerNorm over cols, applied to both in fp64) when given — ||a^ - b^||^2, ||b^||^2,
+    ||a^||^2, a^ . b^ in slots 0-3 and, with a target ``t`` (rows, cols), ||t - a||^2, ||t - b||^2, (a - b) . (t - b) on the raw
+    rows in slots 4-6.  Row strides may differ from cols (multiples of 4); cols % 4 == 0 and <= 2048, else the library refuses
+    the call before it launches anything.  ``out``: a contiguous (rows, 8) f64 tensor to write into."""
+    if a.dim() != 2 or a.shape != b.shape or (t is not None and t.shape != a.shape):
+        raise EmcidHipError(f"score_rows: a, b (and t) must be matrices of one shape (got {tuple(a.shape)}, {tuple(b.shape)}"
+                            f"{', ' + str(tuple(t.shape)) if t is not None else ''})")
+    rows, cols = a.shape
+    for x, nm in ((a, "a"), (b, "b"), (t, "t")):
+        if x is not None and (x.stride(1) != 1 or x.device != a.device):
+            raise EmcidHipError(f"score_rows: {nm} must have unit column stride and live on {a.device}")
+    if ln is not None and (ln.weight is None or ln.bias is None or tuple(ln.normalized_shape) != (cols,)
+                           or not ln.weight.is_contiguous() or not ln.bias.is_contiguous()):
+        raise EmcidHipError("score_rows: a LayerNorm over the last dimension with contiguous affine parameters")
+    if out is None:
+        out = torch.empty(rows, 8, dtype=torch.float64, device=a.device)
+    if out.dtype != torch.float64 or tuple(out.shape) != (rows, 8) or not out.is_contiguous() or out.device != a.device:
+        raise EmcidHipError(f"score_rows: out must be a contiguous ({rows}, 8) f64 tensor on {a.device}")
+    _check(load().emcid_score_rows_f32(
+        _ptr(a, torch.float32, "a"), a.stride(0), _ptr(b, torch.float32, "b"), b.stride(0), _ptr(t, torch.float32, "t"),
+        t.stride(0) if t is not None else 0, _ptr(ln.weight, torch.float32, "gamma") if ln is not None else None,
+        _ptr(ln.bias, torch.float32, "beta") if ln is not None else None, float(ln.eps) if ln is not None else 0.0, rows, cols,
+        _ptr(out, torch.float64, "out"), _stream(a)), "emcid_score_rows_f32")
+    return out
+
+
+def score_chains(node: torch.Tensor, anc: torch.Tensor, depth: torch.Tensor, end_node: torch.Tensor,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B, 4) f64 in HBM, one launch (emcid_score_chains_f64): per prompt the max, the mean and the end-node value of
+    sqrt(node[u, 0] / node[u, 1]) over the chain ``anc[e, 0 .. depth[e]]`` of its end node e = ``end_node[p]``, and the chain
+    position of the max.  ``node`` (U, 8) f64 (``score_rows``' result), ``anc`` (U, S) int32, ``depth`` (U,) int32 — a trie's own
+    arrays —, ``end_node`` (B,) int64."""
+    U = node.shape[0]
+    if node.dim() != 2 or node.shape[1] != 8 or not node.is_contiguous():
+        raise EmcidHipError(f"score_chains: node must be a contiguous (U, 8) f64 tensor (got {tuple(node.shape)})")
+    if anc.dim() != 2 or anc.shape[0] != U or anc.stride(1) != 1 or depth.shape != (U,) or not depth.is_contiguous():
+        raise EmcidHipError(f"score_chains: anc (U, S) and depth (U,) must describe the {U} nodes (got {tuple(anc.shape)}, "
+                            f"{tuple(depth.shape)})")
+    if end_node.dim() != 1 or end_node.numel() == 0 or not end_node.is_contiguous():
+        raise EmcidHipError("score_chains: end_node must be a non-empty contiguous (B,) int64 tensor")
+    if any(x.device != node.device for x in (anc, depth, end_node)):
+        raise EmcidHipError(f"score_chains: every operand must live on {node.device}")
+    B = end_node.numel()
+    if out is None:
+        out = torch.empty(B, 4, dtype=torch.float64, device=node.device)
+    if out.dtype != torch.float64 or tuple(out.shape) != (B, 4) or not out.is_contiguous() or out.device != node.device:
+        raise EmcidHipError(f"score_chains: out must be a contiguous ({B}, 4) f64 tensor on {node.device}")
+    _check(load().emcid_score_chains_f64(
+        _ptr(node, torch.float64, "node"), U, _ptr(anc, torch.int32, "anc"), anc.stride(0), _ptr(depth, torch.int32, "depth"),
+        _ptr(end_node, torch.int64, "end_node"), B, _ptr(out, torch.float64, "out"), _stream(node)), "emcid_score_chains_f64")
+    return out
 
 
 def cov_factor_fold(src: CovFactors, state: PreservedKeys, layer_index: int, cov: Optional[torch.Tensor], lam: float,

@@ -493,6 +493,36 @@ int emcid_session_refold_update_f64(void* cov_ws, int64_t n_layers, int64_t d, i
 int emcid_cov_factor_refactor_f64(void* cov_ws, int64_t workspace_bytes, int64_t n_layers, int64_t d, int* info_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The readout of an edit SCORE (entry points added under ABI 16; emcid_main.EditScorer: what an edit did to the text encoder's
+ * own output — no counterpart in the reference, which judges an edit by generating images, experiments/emcid_test.py).  Two
+ * launches, one each, no workspace, no host synchronisation; one wave per row / prompt, sums by shuffles in a fixed order, so two
+ * calls on the same inputs give the same bits.
+ *
+ * emcid_score_rows_f32: per row r < rows of the fp32 matrices a [rows][lda], b [rows][ldb] and, when given, t [rows][ldt], every
+ * value converted to fp64 before it is used, out [rows][8] f64:
+ *     gamma, beta given (both or neither, [cols] fp32): a^ = LayerNorm(a), b^ = LayerNorm(b) in fp64 (two-pass mean and variance,
+ *     eps as given), else a^ = a, b^ = b
+ *         out[r][0] = ||a^ - b^||^2    out[r][1] = ||b^||^2    out[r][2] = ||a^||^2    out[r][3] = a^ . b^
+ *     t given, on the raw rows
+ *         out[r][4] = ||t - a||^2      out[r][5] = ||t - b||^2  out[r][6] = (a - b) . (t - b)
+ *     out[r][7] and the slots not asked for are 0.
+ * a^ - b^ is formed from a - b (exact in fp64), never from the two normalised rows: rows that agree to 1e-7 still get a
+ * difference good to fp64 rounding, and identical rows give exactly 0 in slots 0 and 6.  cols % 4 == 0, cols <= 2048, leading
+ * dimensions multiples of 4 and >= cols, 16-byte aligned pointers; anything else is EMCID_ERR_BAD_ARG and nothing is launched.
+ *
+ * emcid_score_chains_f64: per prompt p < B with e = end_node[p], over the chain of trie nodes u = anc[e][0 .. depth[e]] (anc
+ * [U][ld_anc] int32, depth [U] int32: the arrays of the prefix-trie forward) and r(u) = sqrt(node[u][0] / node[u][1]) — node
+ * [U][8] f64, the first entry point's output; r = 0 when both sums are 0 —
+ *     out[p][0] = max r    out[p][1] = mean r    out[p][2] = r(e)    out[p][3] = chain position of the max (the first on a tie)
+ * Chains of up to 128 nodes.  An end node or chain entry outside [0, U), or a chain longer than 128 or than ld_anc, reads
+ * nothing: that prompt's four outputs are NaN.
+ * ------------------------------------------------------------------------------------------- */
+int emcid_score_rows_f32(const float* a, int64_t lda, const float* b, int64_t ldb, const float* t, int64_t ldt, const float* gamma,
+                         const float* beta, float eps, int64_t rows, int64_t cols, double* out, void* stream);
+int emcid_score_chains_f64(const double* node, int64_t U, const int32_t* anc, int64_t ld_anc, const int32_t* depth,
+                           const int64_t* end_node, int64_t B, double* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Fallback with the reference's own solver semantics.  torch.linalg.solve (reference: emcid/emcid_main.py:1045-1048) is
  * LAPACK getrf + getrs: LU with partial pivoting, which returns numbers for ANY nonsingular system, whereas the Cholesky
  * paths above stop at a non-positive pivot (info_dev).  emcid_edit_layer_lu_f64 runs one edited layer through a blocked
