@@ -144,12 +144,15 @@ struct EditWorkspace {
 // dependent launches on h rows (~140 us at N = 1000, latency-bound); against an explicit XS = inv(LS) it is two GEMMs against a
 // triangle, Z^T = (RT XS^T) XS.  XT: XS transposed, as it rode in the factorization (XrowJob), or nullptr when the fused schedule
 // did not run.  Then XS is built into `full_inv` [Np, Np] (the callers pass S, which the factorization has consumed) up to
-// Np = 4096; beyond that, or without `full_inv`, the substitution stays.
+// Np = 4096 and where the y2_doubles of Y2 hold that build's scratch; beyond that, or without `full_inv`, the substitution stays
+// (schur_rhs_form, spd_solve.h).
 int solve_schur_rhs(const double* R, int64_t hp, int64_t h, int64_t Np, const double* LS, const double* invS, const double* XT,
-                    double* full_inv, double* RT, double* Y2, hipStream_t st) {
+                    double* full_inv, double* RT, double* Y2, int64_t y2_doubles, hipStream_t st) {
+    if (y2_doubles < hp * Np) return fail(EMCID_ERR_WORKSPACE, __func__, "RT / Y2 hold fewer than h rows of Np (h > d rounded up to 128)");
+    const int form = schur_rhs_form(Np, XT != nullptr, full_inv != nullptr, y2_doubles);
     hipLaunchKernelGGL(transpose_f64_kernel, dim3((unsigned)((hp + 31) / 32), (unsigned)(Np / 32)), dim3(256), 0, st, R, hp, RT, Np,
                        (int)Np, (int)hp);
-    if (XT) {
+    if (form == EMCID_SCHUR_XROW) {
         ScopedProf sp(KC_TRSM_DIAG, st);
         GemmShape f{RT, Np, XT, Np, (int)h, (int)Np, (int)Np, 0};
         f.tri = 1; f.pair = 1;       // B(k, n) = XS[n][k] = Xt[k][n], zero for k > n
@@ -157,8 +160,8 @@ int solve_schur_rhs(const double* R, int64_t hp, int64_t h, int64_t Np, const do
         GemmShape b{Y2, Np, XT, Np, (int)h, (int)Np, (int)Np, 0};
         b.tri = 2; b.pair = 1;       // B(k, n) = XS[k][n] = Xt[n][k], zero for k < n
         launch_gemm_f64<true, true>(b, EpiAxpby{RT, Np, 1.0, 0.0}, st);
-    } else if (full_inv && Np <= 4096) {
-        EMCID_TRY(build_full_inverse(LS, Np, Np, invS, full_inv, Y2, 1, 0, 0, st));
+    } else if (form == EMCID_SCHUR_FULL_INVERSE) {
+        EMCID_TRY(build_full_inverse(LS, Np, Np, invS, full_inv, Y2, y2_doubles, 1, 0, 0, st));
         ScopedProf sp(KC_TRSM_DIAG, st);
         GemmShape f{RT, Np, full_inv, Np, (int)h, (int)Np, (int)Np, 0};
         f.tri = 1; f.pair = 1;       // B(k, n) = XS[n][k], zero for k > n
@@ -325,7 +328,7 @@ int emcid_cov_inverse_f64(void* cov_factor_ws, int64_t n_layers, int64_t d, int6
     const double *Lb = cov.L(cov_factor_ws, first_layer), *Ib = cov.I(cov_factor_ws, first_layer);
     double* Xb = cov.X(cov_factor_ws, first_layer);
     return with_graph(make_key(GRAPH_COV_INVERSE, {Mb, Lb, Ib, Xb}, {dp, count}), (hipStream_t)stream, [&](hipStream_t s) {
-        return build_full_inverse(Lb, dp, dp, Ib, Xb, Mb, (int)count, cov.s_mat, cov.s_inv, s);   // batched over the range
+        return build_full_inverse(Lb, dp, dp, Ib, Xb, Mb, cov.s_mat, (int)count, cov.s_mat, cov.s_inv, s);   // batched over the range
     });
 }
 
@@ -401,6 +404,22 @@ static double* dual_block(void* workspace, int64_t N, int64_t d, int64_t h, int6
 int64_t emcid_edit_dual_workspace_bytes(int64_t N, int64_t d, int64_t h) {
     if (N <= 0 || d <= 0 || h <= 0) return 0;
     return DualWorkspace(N, d, h).total * (int64_t)sizeof(double);
+}
+
+/* any block of a dual workspace by name, with its length (tests read the intermediates of the chain through this) */
+double* emcid_edit_dual_block(void* workspace, int64_t N, int64_t d, int64_t h, int which, int64_t* doubles_out) {
+    if (doubles_out) *doubles_out = -1;
+    int64_t off = 0, n = 0;
+    if (!workspace || N <= 0 || d <= 0 || h <= 0 || !DualWorkspace(N, d, h).block(which, &off, &n)) return nullptr;
+    if (doubles_out) *doubles_out = n;
+    return (double*)workspace + off;
+}
+
+/* how stage 2 of the apply-only form will solve Z = S^-1 Rt for these dimensions: EMCID_SCHUR_* (host only, launches nothing) */
+int emcid_edit_dual_schur_form(int64_t N, int64_t d, int64_t h) {
+    if (N <= 0 || d <= 0 || h <= 0) return -1;
+    const DualWorkspace ws(N, d, h);
+    return schur_rhs_form(ws.Np, cholesky_takes_shadow(ws.Np), true, ws.y2_doubles());
 }
 
 /* what stage 1 of the adj_k form and of the apply-only form ask of the same argument list (a macro: the message names the entry) */
@@ -588,7 +607,7 @@ int emcid_edit_dual_apply_stage2_f64(int64_t N, int64_t d, int64_t h, const void
         const XrowJob xj{XT, Np, TT};
         EMCID_TRY(cholesky_impl(S, LS, Np, Np, invS, info_dev, q, shadow ? &job : nullptr, xrow ? &xj : nullptr));
         // RT[h, Np] = Rt^T ; Z^T = RT S^-1 (two solves with h rows)
-        EMCID_TRY(solve_schur_rhs(R, hp, h, Np, LS, invS, xrow ? XT : nullptr, S, RT, Y2, q));
+        EMCID_TRY(solve_schur_rhs(R, hp, h, Np, LS, invS, xrow ? XT : nullptr, S, RT, Y2, ws.y2_doubles(), q));
         if (!shadow && !p_first) {
             ScopedProf sp(KC_DELTA_W, q);       // V[h, dp] = Z^T Yt
             GemmShape g{RT, Np, Yt, dp, (int)h, (int)dp, (int)Np, 0};
@@ -691,7 +710,7 @@ int emcid_edit_dual_cols_stage2_f64(int64_t N, int64_t d, int64_t h, const void*
         const XrowJob xj{base + ws.off_XT, Np, base + ws.off_TT};
         EMCID_TRY(cholesky_impl(S, LS, Np, Np, invS, info_dev, q, nullptr, xrow ? &xj : nullptr));
         // RT := Z^T, against the inverse that rode in the factorization or by substitution
-        EMCID_TRY(solve_schur_rhs(R, hp, h, Np, LS, invS, xrow ? xj.Xt : nullptr, nullptr, RT, Y2, q));
+        EMCID_TRY(solve_schur_rhs(R, hp, h, Np, LS, invS, xrow ? xj.Xt : nullptr, nullptr, RT, Y2, ws.y2_doubles(), q));
         {
             ScopedProf sp(KC_DELTA_W, q);       // V[h, w] = Z^T Yc
             GemmShape g{RT, Np, Yc, dp, (int)h, w, (int)Np, 0};

@@ -349,7 +349,7 @@ int emcid_cov_factor_fold_f64(const void* src_ws, double lam_ratio, const double
                         fill_base ? C : nullptr, d, lam, (float)(1.0 - edit_weight), st);
     hipLaunchKernelGGL(fold_copy_lower_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, st, base, Mb, (int)dp, 1.0, 0);
     EMCID_TRY(cholesky_serial(Mb, Lb, dp, dp, Ib, info_dev, st, 1, cov.s_mat, cov.s_inv));
-    EMCID_TRY(build_full_inverse(Lb, dp, dp, Ib, Xb, Mb, 1, cov.s_mat, cov.s_inv, st));
+    EMCID_TRY(build_full_inverse(Lb, dp, dp, Ib, Xb, Mb, cov.s_mat, 1, cov.s_mat, cov.s_inv, st));
     EMCID_CHECK_LAUNCH();
     return EMCID_OK;
 }
@@ -431,7 +431,7 @@ int emcid_edit_layer_dual_preserve_f64(const float* K, const float* Zc, const fl
     double* Lkp = Lp + M * ldl;
     EMCID_TRY(session_append_rows(k, N, Yp, ldy, Lp, ldl, tile_inv, M, info_dev, st, __func__));
     // RT[h, Np] = Rt^T ; Zk^T = RT T^-1
-    EMCID_TRY(solve_schur_rhs(R, ws.hp, h, Np, k.LS, k.invS, cholesky_takes_shadow(Np) ? k.XT : nullptr, k.S, RT, Y2, st));
+    EMCID_TRY(solve_schur_rhs(R, ws.hp, h, Np, k.LS, k.invS, cholesky_takes_shadow(Np) ? k.XT : nullptr, k.S, RT, Y2, ws.y2_doubles(), st));
     // ZT = [Zp^T | Zk^T] [h, M + N]: then V = ZT [Yp; Yk] is ONE product over the state's rows, the new ones included
     hipLaunchKernelGGL(copy2d_f64_kernel, dim3((unsigned)h), dim3(256), 0, st, RT, Np, ZT + M, cp, (int)h, (int)N, 1.0);
     if (M > 0) {

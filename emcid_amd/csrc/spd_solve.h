@@ -76,8 +76,10 @@ void trsm_backward(const double* L, int64_t ldl, int64_t n, int blk, const doubl
                    int64_t ldo, int rows, hipStream_t st);
 int cholesky_solve_impl(const double* L, int64_t dp, int64_t lda, const double* invw, double* Bt, double* Yt, int64_t Mrows,
                         int64_t ldb, hipStream_t st);
-int build_full_inverse(const double* L, int64_t dp, int64_t lda, const double* invw, double* X, double* T, int nbatch,
-                       int64_t s_mat, int64_t s_inv, hipStream_t st);
+// (T holds t_doubles per factor; fewer than full_inverse_scratch_doubles(dp, lda) is an error before anything is launched)
+int64_t full_inverse_scratch_doubles(int64_t dp, int64_t lda);
+int build_full_inverse(const double* L, int64_t dp, int64_t lda, const double* invw, double* X, double* T, int64_t t_doubles,
+                       int nbatch, int64_t s_mat, int64_t s_inv, hipStream_t st);
 constexpr int kStreamKWgs = 256;      // runs of the stream-K products against X (apply_inverse_*), and what their workspace is sized for
 void apply_inverse_forward(const double* X, int64_t dp, const double* Kt, double* Yt, int rows, hipStream_t st,
                            double* sk_work = nullptr);
@@ -127,11 +129,36 @@ struct DualWorkspace {
         off_TT = o; o += Np * NB;                                     // ... and its per-step scratch
         total = o;
     }
+    int64_t y2_doubles() const { return dp * Np; }
+    // every block by name (emcid_edit_dual_block, include/emcid_hip.h: the numbers are the EMCID_DUAL_* constants there)
+    bool block(int which, int64_t* off, int64_t* doubles) const {
+        const int64_t offs[] = {off_K, off_P, off_Y, off_R, off_S, off_LS, off_invS, off_PT, off_Y2, off_V, off_U, off_SK, off_XT, off_TT, total};
+        if (which == EMCID_DUAL_SK_COUNTERS) {      // the tail of the stream-K block: what has to be zero between launches
+            *off = off_XT - 8192;
+            *doubles = 8192;
+            return true;
+        }
+        if (which < 0 || which > EMCID_DUAL_TT) return false;
+        *off = offs[which];
+        *doubles = offs[which + 1] - offs[which];
+        return true;
+    }
 };
+
+// How solve_schur_rhs forms Z^T = RT S^-1 when no inverse rode in the factorization (Np > 2048 or Np = 128).  The explicit
+// inverse is built with `scratch_doubles` of Y2 as build_full_inverse's T: a dual workspace holds dp * Np there, which is too
+// little for a d well below N (d = 768 keys, 2100 concepts: 1151 * 2176 + 1024 doubles asked, 768 * 2176 held), and then, as
+// beyond Np = 4096, the solve is the block substitution.  The one statement of the condition: the branch and the entry points'
+// form report (emcid_edit_dual_schur_form) both call it, and build_full_inverse refuses a smaller T before it launches.
+inline int schur_rhs_form(int64_t Np, bool have_xt, bool have_full_inv, int64_t scratch_doubles) {
+    if (have_xt) return EMCID_SCHUR_XROW;
+    if (have_full_inv && Np <= 4096 && full_inverse_scratch_doubles(Np, Np) <= scratch_doubles) return EMCID_SCHUR_FULL_INVERSE;
+    return EMCID_SCHUR_SUBSTITUTION;
+}
 
 // ---- edit_solve.hip -----------------------------------------------------------------------------------------------------------
 int solve_schur_rhs(const double* R, int64_t hp, int64_t h, int64_t Np, const double* LS, const double* invS, const double* XT,
-                    double* full_inv, double* RT, double* Y2, hipStream_t st);
+                    double* full_inv, double* RT, double* Y2, int64_t y2_doubles, hipStream_t st);
 
 // ---- element-wise kernels more than one unit launches (internal linkage: every unit carries its own copy) ---------------------
 

@@ -6,6 +6,8 @@
 // Everything dense runs through gemm_f64.h (v_mfma_f64_16x16x4_f64).  The Cholesky is right-looking
 // with NB = 128: a single-workgroup LDS leaf factors the diagonal block and inverts it, so the panel
 // solve and every later triangular solve are MFMA GEMMs against the inverted diagonal blocks.
+#include <vector>
+
 #include "spd_solve.h"
 
 namespace emcid {
@@ -1126,7 +1128,7 @@ int cholesky_solve_impl(const double* L, int64_t dp, int64_t lda, const double* 
 // with the diagonal OB-blocks taken from build_block_inverses.  Three quarters of the ~dp^3/3 flops sit in the two
 // products of the top split (dp/2 cubed, one operand triangular: its zero part is skipped), which is what makes this
 // form run at GEMM rates; a block-row recurrence has the same flops in 512-row slivers.
-// T: scratch, nbatch x (>= (dp/2)^2 with leading dimension lda) doubles, stride s_mat.  Only the lower triangle of X
+// T: scratch, nbatch x t_doubles >= full_inverse_scratch_doubles(dp, lda) doubles, stride s_mat.  Only the lower triangle of X
 // (and the zeros inside its diagonal 128-blocks) is written; consumers never read anything else.
 __global__ __launch_bounds__(256) void copy_diag_inverse_kernel(const double* __restrict__ invw, int64_t s_inv, double* __restrict__ X,
                                                                  int64_t ldx, int64_t s_x, int64_t dp) {
@@ -1140,17 +1142,12 @@ __global__ __launch_bounds__(256) void copy_diag_inverse_kernel(const double* __
     for (int j = threadIdx.x; j < (hi < w ? hi : w); j += 256) dst[j] = (j <= i) ? src[j] : 0.0;
 }
 
-int build_full_inverse(const double* L, int64_t dp, int64_t lda, const double* invw, double* X, double* T, int nbatch,
-                       int64_t s_mat, int64_t s_inv, hipStream_t st) {
-    ScopedProf sp(KC_INV_BUILD, st);
-    hipLaunchKernelGGL(copy_diag_inverse_kernel, dim3((unsigned)dp, (unsigned)nbatch), dim3(256), 0, st, invw, s_inv, X, lda, s_mat, dp);
+// The recursion over block ranges [b0, b1), as the list of its steps in the order they run.  When the two halves of a range are the
+// same problem (equal block counts, no short last block) they are solved ONCE with the copy count doubled: `reps` copies of the
+// range sit `stride` blocks apart on the diagonal and share every launch through the GEMM's second batch dimension.
+struct InvStep { int b0, mid, b1, reps, stride; };
+static void full_inverse_steps(int64_t dp, std::vector<InvStep>& out) {
     const int nob = (int)((dp + OB - 1) / OB);
-    // 32x64 tiles in mirrored pairs: 1.06 ms for 4 x 3072^2 vs 1.30 ms with the launcher's own choice
-    // (scripts/inverse_alone.py sweeps these)
-    constexpr int cfg_a = 2, cfg_b = 2, pair_ = 1;
-    // Recursion over block ranges [b0, b1).  When the two halves of a range are the same problem (equal block counts, no
-    // short last block) they are solved ONCE with the copy count doubled: `reps` copies of the range sit `stride` blocks
-    // apart on the diagonal and share every launch through the GEMM's second batch dimension.
     const bool regular = dp % OB == 0;
     std::function<void(int, int, int, int)> rec = [&](int b0, int b1, int reps, int stride) {
         const int n = b1 - b0;
@@ -1162,25 +1159,59 @@ int build_full_inverse(const double* L, int64_t dp, int64_t lda, const double* i
             rec(b0, mid, reps, stride);
             rec(mid, b1, reps, stride);
         }
-        const int64_t r0 = (int64_t)b0 * OB, rm = (int64_t)mid * OB, r1 = (int64_t)b1 * OB < dp ? (int64_t)b1 * OB : dp;
+        out.push_back(InvStep{b0, mid, b1, reps, stride});
+    };
+    rec(0, nob, 1, 0);
+}
+
+// What build_full_inverse asks of T, per factor: a step with m = r1 - rm rows below the split and nn = rm - r0 columns left of it
+// writes its `reps` copies as reps * m rows of nn doubles at leading dimension lda, from T[0] on, so it reaches
+// (reps * m - 1) * lda + nn doubles.  reps * m is the same at every level of a regular dp (dp / 2 rows: (dp / 2 - 1) * lda + dp / 2);
+// with a short last block the top split is the largest, m = dp - 512 * (ceil(dp / 512) / 2) rows.
+int64_t full_inverse_scratch_doubles(int64_t dp, int64_t lda) {
+    std::vector<InvStep> steps;
+    full_inverse_steps(dp, steps);
+    int64_t need = 0;
+    for (const InvStep& s : steps) {
+        const int64_t r0 = (int64_t)s.b0 * OB, rm = (int64_t)s.mid * OB, r1 = (int64_t)s.b1 * OB < dp ? (int64_t)s.b1 * OB : dp;
+        const int64_t reach = (s.reps * (r1 - rm) - 1) * lda + (rm - r0);
+        if (reach > need) need = reach;
+    }
+    return need;
+}
+
+int build_full_inverse(const double* L, int64_t dp, int64_t lda, const double* invw, double* X, double* T, int64_t t_doubles,
+                       int nbatch, int64_t s_mat, int64_t s_inv, hipStream_t st) {
+    // before the first launch: a scratch that is too small would be written past its end
+    const int64_t need = full_inverse_scratch_doubles(dp, lda);
+    if (t_doubles < need || (nbatch > 1 && s_mat < need))
+        return fail(EMCID_ERR_WORKSPACE, "build_full_inverse", "scratch T smaller than full_inverse_scratch_doubles(dp, lda)");
+    ScopedProf sp(KC_INV_BUILD, st);
+    hipLaunchKernelGGL(copy_diag_inverse_kernel, dim3((unsigned)dp, (unsigned)nbatch), dim3(256), 0, st, invw, s_inv, X, lda, s_mat, dp);
+    // 32x64 tiles in mirrored pairs: 1.06 ms for 4 x 3072^2 vs 1.30 ms with the launcher's own choice
+    // (scripts/inverse_alone.py sweeps these)
+    constexpr int cfg_a = 2, cfg_b = 2, pair_ = 1;
+    std::vector<InvStep> steps;
+    full_inverse_steps(dp, steps);
+    for (const InvStep& s : steps) {
+        const int64_t r0 = (int64_t)s.b0 * OB, rm = (int64_t)s.mid * OB, r1 = (int64_t)s.b1 * OB < dp ? (int64_t)s.b1 * OB : dp;
         const int m = (int)(r1 - rm), nn = (int)(rm - r0);
-        const int64_t hop = (int64_t)stride * OB * (lda + 1), thop = (int64_t)m * lda;      // between copies: diagonal / scratch
+        const int64_t hop = (int64_t)s.stride * OB * (lda + 1), thop = (int64_t)m * lda;      // between copies: diagonal / scratch
         GemmShape a{L + rm * lda + r0, lda, X + r0 * lda + r0, lda, m, nn, nn, 0, s_mat, s_mat, nbatch};
-        a.sA2 = hop; a.sB2 = hop; a.batch2 = reps;
+        a.sA2 = hop; a.sB2 = hop; a.batch2 = s.reps;
         a.tri = 2;   // B(k, n) = X11[k][n], zero for k < n
         a.pair = pair_;
         EpiAxpby ea{T, lda, 1.0, 0.0, s_mat};
         ea.sC2 = thop;
         launch_gemm_f64<true, false>(a, ea, st, cfg_a);
         GemmShape b{X + rm * lda + rm, lda, T, lda, m, nn, m, 0, s_mat, s_mat, nbatch};
-        b.sA2 = hop; b.sB2 = thop; b.batch2 = reps;
+        b.sA2 = hop; b.sB2 = thop; b.batch2 = s.reps;
         b.tri = 4;   // A(m, k) = X22[m][k], zero for k > m
         b.pair = pair_;
         EpiAxpby eb{X + rm * lda + r0, lda, -1.0, 0.0, s_mat};
         eb.sC2 = hop;
         launch_gemm_f64<true, false>(b, eb, st, cfg_b);
-    };
-    rec(0, nob, 1, 0);
+    }
     return check_launch("build_full_inverse");
 }
 
@@ -1323,6 +1354,19 @@ int emcid_cholesky_solve_f64(const double* L, int64_t dp, int64_t lda, const dou
     EMCID_CHECK_ARG(L && invdiag && Bt && Yt && dp > 0 && dp % NB == 0 && Np > 0 && ldb >= dp && lda >= dp);
     EMCID_CHECK_ARG(aligned16(L) && aligned16(Bt) && aligned16(Yt) && lda % 2 == 0 && ldb % 2 == 0);
     return cholesky_solve_impl(L, dp, lda, invdiag, Bt, Yt, Np, ldb, (hipStream_t)stream);
+}
+
+int64_t emcid_full_inverse_scratch_doubles(int64_t dp, int64_t lda) {
+    if (dp <= 0 || dp % NB != 0 || lda < dp || lda >= (int64_t)1 << 31) return -1;
+    return full_inverse_scratch_doubles(dp, lda);
+}
+
+int emcid_full_inverse_f64(const double* L, int64_t dp, int64_t lda, const double* invdiag, double* X, double* scratch,
+                           int64_t scratch_doubles, void* stream) {
+    EMCID_CHECK_ARG(L && invdiag && X && dp > 0 && dp % NB == 0 && lda >= dp && lda % 2 == 0 && lda < (int64_t)1 << 31);
+    EMCID_CHECK_ARG((scratch || scratch_doubles == 0) && scratch_doubles >= 0);
+    EMCID_CHECK_ARG(aligned16(L) && aligned16(invdiag) && aligned16(X) && aligned16(scratch));
+    return build_full_inverse(L, dp, lda, invdiag, X, scratch, scratch_doubles, 1, 0, 0, (hipStream_t)stream);
 }
 
 }  // extern "C"

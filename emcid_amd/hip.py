@@ -40,7 +40,10 @@ EXPORTS = [
     "emcid_split_rows_f16", "emcid_linear_sp16_f32", "emcid_gram_sp16_workspace_bytes", "emcid_gram_sp16_workspace_bytes_for", "emcid_gram_accumulate_sp16_f32", "emcid_add_layernorm_sp16", "emcid_embed_layernorm_sp16",
     "emcid_tree_attention_sp16", "emcid_tree_attention_sp16_supported", "emcid_clip_workspace_bytes",
     "emcid_clip_layer_head_sp16", "emcid_clip_layer_tail_sp16", "emcid_clip_layers_sp16", "emcid_clip_edit_layer_tail_sp16",
+    "emcid_edit_dual_block", "emcid_edit_dual_schur_form", "emcid_full_inverse_scratch_doubles", "emcid_full_inverse_f64",
 ]
+DUAL_BLOCKS = ["K", "P", "Y", "R", "S", "LS", "INVS", "PT", "Y2", "V", "U", "SK", "XT", "TT", "SK_COUNTERS"]   # EMCID_DUAL_* (include/emcid_hip.h)
+SCHUR_FORMS = ["xrow", "full_inverse", "substitution"]                                                         # EMCID_SCHUR_*
 PROF_CLASSES = ["prep", "assemble", "chol_leaf", "chol_panel", "chol_trail", "trsm_diag", "trsm_update", "delta_w",
                 "gram", "gather", "dgemm", "misc", "inv_build", "chol_inner", "inv_apply", "inv_block", "linear"]
 
@@ -89,6 +92,10 @@ def load():
         "emcid_edit_dual_workspace_bytes": (i64, [i64, i64, i64]),
         "emcid_edit_dual_stage1_f64": (i32, [p, p, p, i64, i64, i64, f64, i32, f64, p, i64, i64, i64, i64, i32, p, i64, p]),
         "emcid_edit_dual_pt": (p, [p, i64, i64, i64]),
+        "emcid_edit_dual_block": (p, [p, i64, i64, i64, i32, C.POINTER(i64)]),
+        "emcid_edit_dual_schur_form": (i32, [i64, i64, i64]),
+        "emcid_full_inverse_scratch_doubles": (i64, [i64, i64]),
+        "emcid_full_inverse_f64": (i32, [p, i64, i64, p, p, p, i64, p]),
         "emcid_edit_dual_stage2_f64": (i32, [i64, i64, i64, f64, p, p, p, p, p, p, i64, p, p]),
         "emcid_edit_dual_apply_stage1_f64": (i32, [p, p, p, i64, i64, i64, f64, i32, f64, p, i64, i64, i64, i64, i32, p, i64, p]),
         "emcid_edit_dual_yt": (p, [p, i64, i64, i64]),
@@ -1130,6 +1137,37 @@ class DualWorkspace:
         self.S = self.buf[off:off + self.Np * self.Np].view(self.Np, self.Np)    # N x N system (column-sharded form: partial sums)
         off = (load().emcid_edit_dual_u(_ptr(self.buf), N, d, h) - self.buf.data_ptr()) // 8
         self.U = self.buf[off:off + hp * self.dp].view(hp, self.dp)[:h]          # U (h, dp) f64 partial sums of the same form
+        # the other blocks of the chain (emcid_edit_dual_block; what each holds after which stage: include/emcid_hip.h)
+        self.hp = hp
+        Np, dp = self.Np, self.dp
+        self.Kt, self.Yt = self.block("K").view(Np, dp), self.block("Y").view(Np, dp)
+        self.Rt = self.block("R").view(Np, hp)
+        self.LS, self.XT = self.block("LS").view(Np, Np), self.block("XT").view(Np, Np)
+        self.RT = self.block("PT").view(dp, Np)              # rows < h: Z^T (apply-only form); adj_k^T padded (adj_k form)
+        self.V = self.block("V").view(hp, dp)[:h]
+        self.sk_counters = self.block("SK_COUNTERS")         # every stream-K launch leaves them zero
+
+    def block(self, name: str) -> torch.Tensor:
+        """Flat f64 view of one block of the workspace (DUAL_BLOCKS)."""
+        n = C.c_int64(0)
+        at = load().emcid_edit_dual_block(_ptr(self.buf), *self.key, DUAL_BLOCKS.index(name), C.byref(n))
+        if not at or n.value < 0:
+            raise EmcidHipError(f"no block {name!r} in a dual workspace")
+        off = (at - self.buf.data_ptr()) // 8
+        return self.buf[off:off + n.value]
+
+    def schur_form(self) -> str:
+        """How stage 2 of the apply-only form will solve Z = S^-1 Rt here (SCHUR_FORMS)."""
+        return SCHUR_FORMS[load().emcid_edit_dual_schur_form(*self.key)]
+
+
+def full_inverse(L: torch.Tensor, inv: torch.Tensor, scratch: torch.Tensor):
+    """Test hook: X = inv(L) (lower triangle) from ``cholesky``'s factor and inverse workspace; ``scratch``: f64,
+    at least emcid_full_inverse_scratch_doubles(dp, ld) elements."""
+    X = torch.zeros_like(L)
+    _check(load().emcid_full_inverse_f64(_ptr(L, torch.float64), L.shape[0], L.stride(0), _ptr(inv), _ptr(X), _ptr(scratch),
+                                         scratch.numel(), _stream(L)), "emcid_full_inverse_f64")
+    return X
 
 
 def edit_layer_dual(K, Zc, zs_t, factors: CovFactors, layer_index: int, edit_weight: float, layers_left: int,

@@ -362,6 +362,28 @@ int emcid_factor_cov_f64(const float* const* C_host_list, int64_t n_layers, int6
 int emcid_cov_factor_rescale_f64(const void* src_ws, void* dst_ws, int64_t workspace_bytes, int64_t n_layers, int64_t d, double a,
                                  int with_inverse, void* stream);
 int64_t emcid_edit_dual_workspace_bytes(int64_t N, int64_t d, int64_t h);
+/* Any block of a dual workspace by name (entry points added under ABI 16; tests and diagnostics read the intermediates of the
+ * chain here instead of restating the layout): its address, and its length in doubles in *doubles_out (may be null).  NULL and
+ * -1 for a null workspace, a non-positive dimension or an unknown name.  Np = N rounded up to 128, dp = d rounded up to 128,
+ * hp = h rounded up to 2.  In the apply-only form, after stage 2:
+ *   K [Np][dp] Kt64 | P [Np][dp] P = Yt X where the shadow / P-first forms ran (stage 1's scratch otherwise; Pt in the adj_k form)
+ *   Y [Np][dp] Yt | R [Np][hp] Rt | S [Np][Np] the system until its factorization consumes it, then inv(LS) where that was built
+ *   LS [Np][Np] lower factor of S | INVS inverted 512-blocks | PT [dp][Np] rows < h: Z^T (adj_k^T padded in the adj_k form)
+ *   Y2 scratch | V [hp][dp] Z^T Yt and U [hp][dp], both only in the forms that go through V | SK stream-K slots, then
+ *   SK_COUNTERS, the 8192 doubles of ticket counters at its end that every launch leaves zero | XT [Np][Np] inv(LS)^T where
+ *   it rode in the factorization (256 <= Np <= 2048) | TT its scratch. */
+enum {
+    EMCID_DUAL_K = 0, EMCID_DUAL_P = 1, EMCID_DUAL_Y = 2, EMCID_DUAL_R = 3, EMCID_DUAL_S = 4, EMCID_DUAL_LS = 5,
+    EMCID_DUAL_INVS = 6, EMCID_DUAL_PT = 7, EMCID_DUAL_Y2 = 8, EMCID_DUAL_V = 9, EMCID_DUAL_U = 10, EMCID_DUAL_SK = 11,
+    EMCID_DUAL_XT = 12, EMCID_DUAL_TT = 13, EMCID_DUAL_SK_COUNTERS = 14
+};
+double* emcid_edit_dual_block(void* workspace, int64_t N, int64_t d, int64_t h, int which, int64_t* doubles_out);
+/* How stage 2 of the apply-only form solves Z = S^-1 Rt at these dimensions (host only, launches nothing; -1: bad dimension):
+ * XROW against the inverse that rode in the fused factorization, FULL_INVERSE against inv(LS) built after the serial one (up
+ * to Np = 4096, and only where the workspace's [dp][Np] scratch holds emcid_full_inverse_scratch_doubles(Np, Np): d must
+ * be about N / 2 or more), SUBSTITUTION by blocks otherwise. */
+enum { EMCID_SCHUR_XROW = 0, EMCID_SCHUR_FULL_INVERSE = 1, EMCID_SCHUR_SUBSTITUTION = 2 };
+int emcid_edit_dual_schur_form(int64_t N, int64_t d, int64_t h);
 int emcid_edit_dual_stage1_f64(const float* K, const float* Zc, const float* zs_t, int64_t N, int64_t d, int64_t h,
                                double edit_weight, int layers_left, double lam_ratio, const void* cov_factor_ws, int64_t n_layers,
                                int64_t layer_index, int64_t n_lo, int64_t n_hi, int use_inverse, void* workspace,
@@ -585,6 +607,12 @@ int emcid_cholesky_f64(double* A, double* L, int64_t dp, int64_t lda, double* in
  * replaces the getrs half of torch.linalg.solve (:1045-1048). */
 int emcid_cholesky_solve_f64(const double* L, int64_t dp, int64_t lda, const double* invdiag,
                              double* Bt, double* Yt, int64_t Np, int64_t ldb, void* stream);
+/* X = inv(L), explicit (lower triangle; [dp][lda]), from the factor and invdiag of emcid_cholesky_f64.  scratch: f64,
+ * scratch_doubles >= emcid_full_inverse_scratch_doubles(dp, lda) (-1: bad dimensions); a smaller one is refused with
+ * EMCID_ERR_WORKSPACE before anything is launched. */
+int64_t emcid_full_inverse_scratch_doubles(int64_t dp, int64_t lda);
+int emcid_full_inverse_f64(const double* L, int64_t dp, int64_t lda, const double* invdiag, double* X, double* scratch,
+                           int64_t scratch_doubles, void* stream);
 /* U = Rt^T Xt (f64, optional) ; dW = float(U) (optional) ; W = W0 + float(U) (optional).  (:1050,:1061) */
 int emcid_delta_w_f64(const double* Rt, int64_t ldr, const double* Xt, int64_t ldx, int64_t Np, int64_t h, int64_t d,
                       const float* W0, float* W, int64_t ldw, float* dW, double* U, void* stream);

@@ -272,7 +272,9 @@ def test_tree_attention_vs_dense_reference(U, H, D, max_depth):
                                               (1000, 5120, 1280, 10000.0, 0.5, 5),       # config 4 full size: Np = 1024 at dp = 5120 (no shadow
                                                                                          # product: two rounds of stream-K / paired tiles)
                                               (1500, 3072, 768, 4000.0, 0.5, 3),         # data/artists/info/erased-1500artists-...: Np = 1536
-                                              (2000, 3072, 768, 4000.0, 0.5, 1)])
+                                              (2000, 3072, 768, 4000.0, 0.5, 1),
+                                              (2100, 3072, 768, 4000.0, 0.5, 2)])        # Np = 2176: past the fused steps (serial chain,
+                                                                                         # short last 512-block, inverse of LS built after it)
 def test_dual_solver_vs_oracle(N, d, h, lam, ew, left):
     """The Woodbury form (batched factor of lam*C', N x N system per layer) against the oracle's fp64 LU."""
     K, Zc, zs, Cov, W0 = _edit_inputs(N, d, h, seed=N + d)
