@@ -1692,8 +1692,8 @@ class EditScorer:
     cross-attention ``rewrite_module_tmp``, a collective ``ConceptShard`` (``ValueError``); and a ``score()`` when a parameter other
     than the edited fc2 weights is not the tensor, at the address, with the in-place version counter it had at construction
     (``ValueError``: the kept states would no longer be this encoder's).  That check is host-only: a write through ``.data`` or a
-    raw pointer to such a parameter is not seen and is the caller's responsibility.  Not done here: SDXL, sharded calls, scoring
-    on the hooked-HF forward, positions behind the EOS."""
+    raw pointer to such a parameter is not seen and is the caller's responsibility.  Not done here: the SDXL pair (that is
+    ``PairEditScorer``), sharded calls, scoring on the hooked-HF forward, positions behind the EOS."""
 
     def __init__(self, pipe, requests: List[Dict], hparams: EMCIDHyperParams, device: Optional[str] = None, holdout=None,
                  cache_name: Optional[str] = None, shard=None, _plan: Optional[EncoderEditPlan] = None):
@@ -1826,6 +1826,266 @@ class EditScorer:
         cos = torch.where(den > 0, dot / den.clamp(min=tiny), torch.zeros_like(dot))
         return EditScore(self.sources, left, cos, resid2.sqrt(), resid02.sqrt(), self.holdout, chains[:, 0].clone(),
                          chains[:, 1].clone(), chains[:, 2].clone(), chains[:, 3].clone())
+
+
+class PairEditScore:
+    """What ``PairEditScorer.score`` read of the SDXL pair of text encoders, as fp64 tensors on the host.
+
+        te1, te2    one ``EditScore`` per encoder: its concept rows (``left``, ``cos``, ``resid``, ``resid0``) and, per holdout
+                    prompt, the drift over that encoder's own columns of ``hidden_states[-2]`` (no final LayerNorm)
+        sources, left, cos, resid, resid0   the rows of te1, then those of te2; sources are (source, token index, encoder 1 | 2)
+    Per holdout prompt, where the UNet is conditioned:
+        drift_max, drift_mean, drift_eos, drift_argmax   as in ``EditScore``, of the ratio over the CONCATENATED token state
+                    [hidden_states[-2] of TE1 ; hidden_states[-2] of TE2]: sqrt((|dh_1|^2 + |dh_2|^2) / (|h0_1|^2 + |h0_2|^2))
+        drift_pooled    ||P (a^ - b^)|| / ||P b^|| of the pooled embedding text_projection(final_layer_norm(H_last[EOS])) of TE2
+                    (a^ now, b^ at construction), or None when text_encoder_2 has no text_projection
+    ``select_point`` takes a list of these as it takes ``EditScore``s: it reads ``left`` and ``drift_max``."""
+
+    def __init__(self, te1: EditScore, te2: EditScore, holdout, drift_max, drift_mean, drift_eos, drift_argmax, drift_pooled=None):
+        self.te1, self.te2, self.holdout = te1, te2, list(holdout)
+        self.sources = [(s, t, 1) for s, t in te1.sources] + [(s, t, 2) for s, t in te2.sources]
+        self.left, self.cos = torch.cat([te1.left, te2.left]), torch.cat([te1.cos, te2.cos])
+        self.resid, self.resid0 = torch.cat([te1.resid, te2.resid]), torch.cat([te1.resid0, te2.resid0])
+        self.drift_max, self.drift_mean, self.drift_eos, self.drift_argmax = drift_max, drift_mean, drift_eos, drift_argmax
+        self.drift_pooled = drift_pooled
+
+    def summary(self) -> Dict[str, float]:
+        out = {"left_median": _median(self.left), "left_max": float(self.left.max()),
+               "drift_max": float(self.drift_max.max()), "drift_median": _median(self.drift_max),
+               "left_median_1": _median(self.te1.left), "left_median_2": _median(self.te2.left)}
+        if self.drift_pooled is not None:
+            out["drift_pooled_max"] = float(self.drift_pooled.max())
+        return out
+
+    def __repr__(self):
+        return "PairEditScore(" + ", ".join(f"{k}={v:.4g}" for k, v in self.summary().items()) + ")"
+
+
+class _PairEncoder:
+    """One encoder of a ``PairEditScorer``: what ``EditScorer`` keeps of its one encoder, with the holdout read one layer earlier
+    (``hidden_states[-2]``, raw) and, ``pooled``, the last layer continued on the EOS rows."""
+
+    def __init__(self, te, graph, layers, plan, ids_h, eos_h, pooled: bool):
+        self.te, self.graph, self.layers, self.pooled = te, graph, layers, pooled
+        self.chunk, self.zs = plan.chunk, plan.resolve_targets()
+        self._state = tuple(plan.chunk.state[1:])
+        plan.chunk.state = None
+        dev = self.zs.device
+        self.trie_h = clip_forward.build_trie(ids_h, eos_h, dev)
+        self._state_h = tuple(clip_forward.run_prefix(graph, self.trie_h, layers[0]))
+        self.frozen = self.signature()
+        Z0, self.H0, self.H0last = self.forward()
+        self.Z0 = Z0.clone()
+        if tuple(self.zs.shape) != tuple(self.Z0.shape):
+            raise ValueError(f"{self.Z0.shape[0]} concept rows of width {self.Z0.shape[1]} and v* of shape {tuple(self.zs.shape)}")
+        self.node = torch.empty(self.H0.shape[0], 8, dtype=torch.float64, device=dev)
+
+    def signature(self):
+        """(name, identity, address, in-place version) of every parameter but the edited fc2 weights — of those: identity alone."""
+        edited = {id(self.graph.layers[l].fc2.weight) for l in self.layers}
+        return tuple((n, id(p)) if id(p) in edited else (n, id(p), p.data_ptr(), p._version) for n, p in self.te.named_parameters())
+
+    def forward(self):
+        """(Z (N, h), H (holdout nodes, h) after the penultimate layer, H_last (B, h) at the EOS rows | None), fp32, on the weights
+        as they are: the replay from the two kept states."""
+        g, ch, first, last = self.graph, self.chunk, self.layers[0], self.layers[-1]
+        box = []
+
+        def on_fc2(li, x, out, mid=None, next_ln=None):
+            # the engine's own Zc of its last layer (EditScorer._forward)
+            if li != last:
+                return out
+            layer = g.layers[li]
+            xf = x.float() if isinstance(x, hip.SplitRows) else x
+            K = hip.gather_mean(xf.unsqueeze(0).expand(ch.lookup_query.numel(), -1, -1), ch.lookup_query, ch.cseg)
+            box.append(clip_forward.linear(K, layer.fc2.weight, layer.fc2.bias, wsp=layer.split_of("fc2")))
+            return None
+
+        clip_forward.run_layers_from(g, ch.trie, self._state, first, last, on_fc2, fc2_by_callback=(last,), edit_callback=True)
+        n_layers = len(g.layers)
+        # hidden_states[-2]: every node, raw; when it lies before the first edited layer it is the kept state itself
+        state = self._state_h if first > n_layers - 2 else \
+            clip_forward.run_layers_from(g, self.trie_h, self._state_h, first, n_layers - 2, None, last_rows_only=False)
+        h_last = None
+        if self.pooled:       # the last layer continued on the distinct EOS nodes, then one row per prompt
+            rows = clip_forward.run_layers_from(g, self.trie_h, state, n_layers - 1, n_layers - 1, None, last_rows_only=True)[0]
+            h_last = rows.index_select(0, self.trie_h.lookup_in_query)
+        if g.guard is not None:
+            g.guard.flush()
+        clip_forward.LAST_PATHS["score_replays"] = clip_forward.LAST_PATHS.get("score_replays", 0) + 1
+        return box[0], state[0], h_last
+
+
+class PairEditScorer:
+    """Scores edits of the SDXL PAIR of text encoders, on the device, where an SDXL UNet is conditioned.
+
+        scorer = PairEditScorer(pipe, requests, hparams, device, holdout=[prompt strings], cache_name=...)   # on the BASELINE weights
+        ... apply_emcid_to_sdxl_text_encoders, or any other edit of the fc2 weights of hparams.layers / hparams.layers_2 ...
+        s = scorer.score()                                                                                  # -> PairEditScore
+
+    For encoder e in {1, 2} — layers ``hparams.layers`` / ``hparams.layers_2``, v* files with suffix "" / "_2" — efficacy is
+    ``EditScorer``'s: Z_e the mean over a concept's prompts of the LAST edited layer's fc2 output at the lookup rows, Z0_e the same
+    on the baseline weights, ``left_e = ||v*_e - Z_e|| / ||v*_e - Z0_e||``, ``cos_e = cos(Z_e - Z0_e, v*_e - Z0_e)``.  The weights are
+    read as they are: after ``apply_emcid_to_sdxl_text_encoders`` TE2 holds W + 2 dW (the reference's double apply,
+    ``SDXL_TE2_DOUBLE_APPLY``) and ``left_2`` reports that overshoot.  Drift follows the conditioning of an SDXL UNet, which takes
+    NO final LayerNorm on the token states but, per token, [hidden_states[-2] of TE1 ; hidden_states[-2] of TE2], and the pooled
+    embedding of TE2: with h_e(u) the raw residual stream after encoder e's penultimate layer at token u of BOS ... EOS and h0_e the
+    same at construction, the token ratio is r(u) = sqrt((|h_1 - h0_1|^2 + |h_2 - h0_2|^2) / (|h0_1|^2 + |h0_2|^2)) (0 when both
+    sums are 0), reduced per prompt as in ``EditScore``; each encoder's own ratio over its own columns is in ``te1`` / ``te2``; and
+    ``drift_pooled = ||P (a^ - b^)|| / ||P b^||`` with a^ = final_layer_norm(H_last[EOS]) of TE2, b^ the same at construction and
+    P = ``text_projection.weight`` — None when text_encoder_2 has no ``text_projection``.  Positions behind the EOS are not scored.
+
+    The constructor prepares each encoder as a call does (same trie, same lookups, v* through ``load_v_stars`` with the encoder's
+    suffix and width; a missing file is an error: Stage 1 never runs), builds a holdout trie per encoder whose lookups are the EOS
+    tokens, runs the unedited leading layers on both tries of both encoders and keeps the four states, then replays once and
+    keeps, per encoder, Z0_e (N, h_e) and the penultimate H0_e (holdout nodes of that trie, h_e), and for TE2 with a projection
+    H0last (B, h_2) at the EOS rows — all fp32 in HBM.
+
+    ``score()`` replays both encoders from the kept states (request trie to the last edited layer; holdout trie to the penultimate
+    layer on every node and, for the pooled embedding, the last layer on the EOS rows), then per encoder ``hip.score_rows`` on
+    (Z, Z0, v*) and on (H, H0) without a LayerNorm and ``hip.score_chains``, once ``hip.score_chains_pair`` and once
+    ``hip.score_pooled``, and ONE pinned readback, the only host synchronisation.  Everything is issued on the current stream.  No
+    weight is moved, every parameter is bit-identical afterwards, two calls in a row return the same bits.
+
+    Refused before anything is launched: ``hparams`` that is not ``EMCIDXLHyperParams`` (``TypeError``); a pipe without
+    ``text_encoder_2``, ``num_edit_tokens != 1``, a collective ``ConceptShard``, two tokenizers that give a holdout prompt different
+    BOS ... EOS lengths, a holdout prompt longer than a position table (``ValueError``); an encoder the prefix-trie forward does not
+    take — not HF CLIP, not fp32 in HBM, fewer than two layers, h % 4 != 0 or h > 2048, a ``text_projection`` with a bias —, a
+    holdout prompt of more than ``SCORE_MAX_CHAIN`` tokens (``clip_forward.UnsupportedEncoder``); a missing v* file
+    (``FileNotFoundError``); and, as in ``EditScorer``, a ``score()`` when a parameter of either encoder other than its edited fc2
+    weights is not the tensor, at the address, with the version counter it had at construction (``ValueError``).  Not done here:
+    an SDXL sweep, sessions, sharded calls, the hooked-HF forward, positions behind the EOS."""
+
+    def __init__(self, pipe, requests: List[Dict], hparams: EMCIDXLHyperParams, device: Optional[str] = None, holdout=None,
+                 cache_name: Optional[str] = None, shard=None):
+        if not isinstance(hparams, EMCIDXLHyperParams):
+            raise TypeError(f"hparams must be EMCIDXLHyperParams, got {type(hparams).__name__}")
+        if getattr(pipe, "text_encoder_2", None) is None or getattr(pipe, "tokenizer_2", None) is None:
+            raise ValueError("PairEditScorer scores the SDXL pair: the pipe has no text_encoder_2 / tokenizer_2 (EditScorer scores one encoder)")
+        if int(getattr(hparams, "num_edit_tokens", 1) or 1) != 1:
+            raise ValueError("num_edit_tokens should be 1 for the SDXL pair")       # (as _sdxl_plans, reference :1246)
+        if _shard_from_env(shard).collective:
+            raise ValueError("PairEditScorer runs on one rank: a collective ConceptShard is not supported")
+        if len(requests) == 0:
+            raise ValueError("PairEditScorer needs at least one request")
+        holdout = list(holdout) if holdout is not None else []
+        if not holdout or not all(isinstance(p, str) for p in holdout):
+            raise ValueError("holdout must be a non-empty list of prompt strings")
+        layer_tmp = getattr(hparams, "layer_module_tmp", None)
+        if layer_tmp is None:
+            raise clip_forward.UnsupportedEncoder("hparams.layer_module_tmp is not set: no prefix-trie forward")
+        for which, layers in ((1, list(hparams.layers)), (2, list(hparams.layers_2))):
+            if not layers or sorted(layers) != layers:
+                raise ValueError(f"the layers of text encoder {which} must be a non-empty list in forward order (got {layers})")
+        found = []
+        for which, te, tok, layers, suffix in ((1, pipe.text_encoder, pipe.tokenizer, list(hparams.layers), ""),
+                                               (2, pipe.text_encoder_2, pipe.tokenizer_2, list(hparams.layers_2), "_2")):
+            try:
+                weights = [nethook.get_parameter(te, f"{hparams.rewrite_module_tmp.format(l)}.weight") for l in layers]
+            except LookupError as e:
+                raise ValueError(f"{hparams.rewrite_module_tmp!r} names no weight of text encoder {which}: {e}") from e
+            w = weights[0]
+            if device is not None and torch.device(device).type != w.device.type:
+                raise ValueError(f"device {device!r} but the weights of text encoder {which} live on {w.device}")
+            if not (w.is_cuda and w.dtype == torch.float32):
+                raise clip_forward.UnsupportedEncoder(f"the prefix-trie forward runs fp32 in HBM (text encoder {which}: {w.dtype} on {w.device})")
+            try:
+                graph = clip_forward.discover_cached(te, layer_tmp)
+                if any(graph.layers[l].fc2.weight is not wl for l, wl in zip(layers, weights)):
+                    raise clip_forward.UnsupportedEncoder("rewrite_module_tmp is not the layer's mlp.fc2")
+            except (IndexError, LookupError) as e:
+                raise clip_forward.UnsupportedEncoder(str(e)) from e
+            h = int(w.shape[0])
+            if len(graph.layers) < 2 or h % 4 or h > hip.SCORE_MAX_COLS:
+                raise clip_forward.UnsupportedEncoder(f"the pair's readout takes encoders of two or more layers and h % 4 == 0, h <= "
+                                                      f"{hip.SCORE_MAX_COLS} (text encoder {which}: {len(graph.layers)} layers, h = {h})")
+            ids_h, eos_h = holdout_tokens(tok, holdout, graph.position_embedding.num_embeddings)
+            found.append((te, tok, layers, suffix, graph, h, ids_h, eos_h))
+        if not np.array_equal(found[0][7], found[1][7]):
+            p = int(np.nonzero(found[0][7] != found[1][7])[0][0])
+            raise ValueError(f"holdout prompt {p} ({holdout[p]!r}) has {int(found[0][7][p]) + 1} tokens BOS ... EOS in the first "
+                             f"tokenizer and {int(found[1][7][p]) + 1} in the second: their token states cannot be concatenated")
+        proj = getattr(pipe.text_encoder_2, "text_projection", None)
+        ln2 = found[1][4].final_layer_norm
+        if proj is not None:
+            h2 = found[1][5]
+            if not (isinstance(proj, torch.nn.Linear) and proj.bias is None and proj.weight.is_cuda and proj.weight.dtype == torch.float32
+                    and proj.weight.shape[1] == h2 and proj.weight.stride(1) == 1 and proj.weight.stride(0) % 4 == 0
+                    and isinstance(ln2, torch.nn.LayerNorm) and ln2.weight is not None and ln2.bias is not None
+                    and ln2.weight.is_cuda and ln2.weight.dtype == torch.float32 and tuple(ln2.normalized_shape) == (h2,)):
+                raise clip_forward.UnsupportedEncoder("the pooled readout takes text_projection as an fp32 nn.Linear without bias over an "
+                                                      f"affine fp32 final LayerNorm of h = {h2} columns")
+        for te, tok, layers, suffix, graph, h, ids_h, eos_h in found:
+            if _any_vstar_missing(requests, hparams, cache_name, suffix):
+                raise FileNotFoundError(f"a v* file (suffix {suffix!r}) of the {len(requests)} requests is missing under {cache_name!r}: "
+                                        f"a PairEditScorer reads the targets an edit was made towards and never runs Stage 1")
+        self.pipe, self.hparams, self.holdout, self.proj, self.ln2 = pipe, hparams, holdout, proj, ln2
+        self.sources = score_row_sources(requests, 1)
+        self.encoders = []
+        with torch.no_grad():
+            for (te, tok, layers, suffix, graph, h, ids_h, eos_h), lam in zip(found, (hparams.mom2_update_weight, hparams.mom2_update_weight_2)):
+                plan = prepare_encoder_edit(
+                    te, tok, requests, layers, hparams.rewrite_module_tmp, float(lam), float(hparams.edit_weight),
+                    lambda suffix=suffix, h=h: load_v_stars(requests, hparams, cache_name, suffix, None, width=h, pin=True),
+                    lambda: {}, ConceptShard(), layer_module_tmp=layer_tmp, num_edit_tokens=1)
+                if plan.chunk is None or plan.graph is not graph or plan.chunk.state is None or plan.chunk.state[0] != layers[0] \
+                        or plan.layers != layers:
+                    raise clip_forward.UnsupportedEncoder("the requests did not take the prefix-trie forward")
+                self.encoders.append(_PairEncoder(te, graph, layers, plan, ids_h, eos_h, pooled=proj is not None and suffix == "_2"))
+        e1, e2 = self.encoders
+        n1, n2, B = e1.Z0.shape[0], e2.Z0.shape[0], len(holdout)
+        if n1 != len(self.sources) or n2 != len(self.sources):
+            raise ValueError(f"{n1} and {n2} concept rows for {len(self.sources)} requests")
+        # one result buffer, one readback: [rows of TE1 | rows of TE2 | chains of TE1 | of TE2 | of the pair | pooled]
+        self._cuts = np.cumsum([0, n1 * 8, n2 * 8, B * 4, B * 4, B * 4, B * 4 if proj is not None else 0]).tolist()
+        self._out = torch.empty(self._cuts[-1], dtype=torch.float64, device=e1.Z0.device)
+        self._host = torch.empty(self._cuts[-1], dtype=torch.float64, pin_memory=True)
+
+    def _part(self, buf, i, width):
+        return buf[self._cuts[i]:self._cuts[i + 1]].view(-1, width)
+
+    def score(self) -> PairEditScore:
+        """Score the weights of both encoders as they are against the baseline of construction (class docstring)."""
+        for which, enc in enumerate(self.encoders, 1):
+            now = enc.signature()
+            if now != enc.frozen:
+                now = dict((s[0], s) for s in now)
+                moved = [s[0] for s in enc.frozen if now.get(s[0]) != s]
+                raise ValueError(f"parameters of text encoder {which} other than the edited fc2 weights changed since this "
+                                 f"PairEditScorer was built ({', '.join(moved[:4]) or 'the parameter list'}"
+                                 f"{', ...' if len(moved) > 4 else ''}): its kept states are no longer this encoder's; build a new one")
+        e1, e2 = self.encoders
+        out = self._out
+        with torch.no_grad():
+            for i, enc in enumerate(self.encoders):
+                Z, H, h_last = enc.forward()
+                hip.score_rows(Z, enc.Z0, t=enc.zs, out=self._part(out, i, 8))
+                hip.score_rows(H, enc.H0, out=enc.node)
+                hip.score_chains(enc.node, enc.trie_h.anc, enc.trie_h.depth, enc.trie_h.lookup_node, out=self._part(out, 2 + i, 4))
+            hip.score_chains_pair(e1.node, e1.trie_h.anc, e1.trie_h.depth, e1.trie_h.lookup_node,
+                                  e2.node, e2.trie_h.anc, e2.trie_h.depth, e2.trie_h.lookup_node, out=self._part(out, 4, 4))
+            if self.proj is not None:
+                hip.score_pooled(h_last, e2.H0last, self.ln2, self.proj.weight, out=self._part(out, 5, 4))
+            self._host.copy_(out, non_blocking=True)
+            torch.cuda.current_stream(out.device).synchronize()
+        host = self._host.clone()
+        tiny = torch.finfo(torch.float64).tiny
+
+        def encoder_score(i):
+            rows, chains = self._part(host, i, 8), self._part(host, 2 + i, 4)
+            moved2, resid2, resid02, dot = rows[:, 0], rows[:, 4], rows[:, 5], rows[:, 6]
+            left = torch.where(resid02 > 0, (resid2 / resid02.clamp(min=tiny)).sqrt(), torch.zeros_like(resid2))
+            den = (moved2 * resid02).sqrt()
+            cos = torch.where(den > 0, dot / den.clamp(min=tiny), torch.zeros_like(dot))
+            return EditScore(self.sources, left, cos, resid2.sqrt(), resid02.sqrt(), self.holdout, chains[:, 0].clone(),
+                             chains[:, 1].clone(), chains[:, 2].clone(), chains[:, 3].clone())
+
+        pair, pooled = self._part(host, 4, 4), None
+        if self.proj is not None:
+            sums = self._part(host, 5, 4)
+            pooled = torch.where(sums[:, 0] > 0, (sums[:, 0] / sums[:, 1].clamp(min=tiny)).sqrt(), torch.zeros_like(sums[:, 0]))
+        return PairEditScore(encoder_score(0), encoder_score(1), self.holdout, pair[:, 0].clone(), pair[:, 1].clone(),
+                             pair[:, 2].clone(), pair[:, 3].clone(), pooled)
 
 
 def sweep_emcid_text_encoder(pipe, requests: List[Dict], hparams: EMCIDHyperParams, grid, device: Optional[str] = None,

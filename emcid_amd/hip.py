@@ -33,7 +33,7 @@ EXPORTS = [
     "emcid_session_release_workspace_bytes", "emcid_session_release_f64",
     "emcid_cov_factor_fold_workspace_bytes", "emcid_cov_factor_fold_f64",
     "emcid_session_refold_update_f64", "emcid_cov_factor_refactor_f64",
-    "emcid_score_rows_f32", "emcid_score_chains_f64",
+    "emcid_score_rows_f32", "emcid_score_chains_f64", "emcid_score_chains_pair_f64", "emcid_score_pooled_f32",
     "emcid_edit_lu_workspace_bytes", "emcid_edit_layer_lu_f64", "emcid_lu_solve_f64",
     "emcid_edit_dual_cols_stage1_f64", "emcid_edit_dual_s", "emcid_edit_dual_u", "emcid_edit_dual_cols_stage2_f64",
     "emcid_apply_update2d_f32", "emcid_linear_f32", "emcid_linear_ws_f32", "emcid_linear_workspace_bytes",
@@ -115,6 +115,8 @@ def load():
         "emcid_cov_factor_refactor_f64": (i32, [p, i64, i64, i64, p, p]),
         "emcid_score_rows_f32": (i32, [p, i64, p, i64, p, i64, p, p, f32, i64, i64, p, p]),
         "emcid_score_chains_f64": (i32, [p, i64, p, i64, p, p, i64, p, p]),
+        "emcid_score_chains_pair_f64": (i32, [p, i64, p, i64, p, p, p, i64, p, i64, p, p, i64, p, p]),
+        "emcid_score_pooled_f32": (i32, [p, i64, p, i64, p, p, f32, p, i64, i64, i64, i64, p, p]),
         "emcid_cholesky_solve_f64": (i32, [p, i64, i64, p, p, p, i64, i64, p]),
         "emcid_edit_dual_cols_stage1_f64": (i32, [p, p, p, i64, i64, i64, f64, i32, f64, p, i64, i64, p, i32, p, i64, p]),
         "emcid_edit_dual_s": (p, [p, i64, i64, i64]),
@@ -1655,20 +1657,25 @@ def score_rows(a: torch.Tensor, b: torch.Tensor, t: Optional[torch.Tensor] = Non
     return out
 
 
+def _check_chain_arrays(who: str, node: torch.Tensor, anc: torch.Tensor, depth: torch.Tensor, end_node: torch.Tensor):
+    U = node.shape[0]
+    if node.dim() != 2 or node.shape[1] != 8 or not node.is_contiguous():
+        raise EmcidHipError(f"{who}: node must be a contiguous (U, 8) f64 tensor (got {tuple(node.shape)})")
+    if anc.dim() != 2 or anc.shape[0] != U or anc.stride(1) != 1 or depth.shape != (U,) or not depth.is_contiguous():
+        raise EmcidHipError(f"{who}: anc (U, S) and depth (U,) must describe the {U} nodes (got {tuple(anc.shape)}, "
+                            f"{tuple(depth.shape)})")
+    if end_node.dim() != 1 or end_node.numel() == 0 or not end_node.is_contiguous():
+        raise EmcidHipError(f"{who}: end_node must be a non-empty contiguous (B,) int64 tensor")
+
+
 def score_chains(node: torch.Tensor, anc: torch.Tensor, depth: torch.Tensor, end_node: torch.Tensor,
                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(B, 4) f64 in HBM, one launch (emcid_score_chains_f64): per prompt the max, the mean and the end-node value of
     sqrt(node[u, 0] / node[u, 1]) over the chain ``anc[e, 0 .. depth[e]]`` of its end node e = ``end_node[p]``, and the chain
     position of the max.  ``node`` (U, 8) f64 (``score_rows``' result), ``anc`` (U, S) int32, ``depth`` (U,) int32 — a trie's own
     arrays —, ``end_node`` (B,) int64."""
+    _check_chain_arrays("score_chains", node, anc, depth, end_node)
     U = node.shape[0]
-    if node.dim() != 2 or node.shape[1] != 8 or not node.is_contiguous():
-        raise EmcidHipError(f"score_chains: node must be a contiguous (U, 8) f64 tensor (got {tuple(node.shape)})")
-    if anc.dim() != 2 or anc.shape[0] != U or anc.stride(1) != 1 or depth.shape != (U,) or not depth.is_contiguous():
-        raise EmcidHipError(f"score_chains: anc (U, S) and depth (U,) must describe the {U} nodes (got {tuple(anc.shape)}, "
-                            f"{tuple(depth.shape)})")
-    if end_node.dim() != 1 or end_node.numel() == 0 or not end_node.is_contiguous():
-        raise EmcidHipError("score_chains: end_node must be a non-empty contiguous (B,) int64 tensor")
     if any(x.device != node.device for x in (anc, depth, end_node)):
         raise EmcidHipError(f"score_chains: every operand must live on {node.device}")
     B = end_node.numel()
@@ -1679,6 +1686,62 @@ def score_chains(node: torch.Tensor, anc: torch.Tensor, depth: torch.Tensor, end
     _check(load().emcid_score_chains_f64(
         _ptr(node, torch.float64, "node"), U, _ptr(anc, torch.int32, "anc"), anc.stride(0), _ptr(depth, torch.int32, "depth"),
         _ptr(end_node, torch.int64, "end_node"), B, _ptr(out, torch.float64, "out"), _stream(node)), "emcid_score_chains_f64")
+    return out
+
+
+def score_chains_pair(node1: torch.Tensor, anc1: torch.Tensor, depth1: torch.Tensor, end_node1: torch.Tensor,
+                      node2: torch.Tensor, anc2: torch.Tensor, depth2: torch.Tensor, end_node2: torch.Tensor,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B, 4) f64 in HBM, one launch (emcid_score_chains_pair_f64): ``score_chains`` over the concatenated columns of two encoders.
+    Per prompt p and chain position j, with c_e the chain ``anc_e[end_node_e[p], 0 .. depth_e[end_node_e[p]]]`` in encoder e's own
+    trie, r_j = sqrt((node1[c_1[j], 0] + node2[c_2[j], 0]) / (node1[c_1[j], 1] + node2[c_2[j], 1])); the max, the mean, the value at
+    the end and the chain position of the max.  A prompt whose two chains differ in length (or leave their tries) gets four NaN."""
+    _check_chain_arrays("score_chains_pair", node1, anc1, depth1, end_node1)
+    _check_chain_arrays("score_chains_pair", node2, anc2, depth2, end_node2)
+    B = end_node1.numel()
+    if end_node2.numel() != B:
+        raise EmcidHipError(f"score_chains_pair: {B} end nodes in the first trie, {end_node2.numel()} in the second")
+    if any(x.device != node1.device for x in (anc1, depth1, end_node1, node2, anc2, depth2, end_node2)):
+        raise EmcidHipError(f"score_chains_pair: every operand must live on {node1.device}")
+    if out is None:
+        out = torch.empty(B, 4, dtype=torch.float64, device=node1.device)
+    if out.dtype != torch.float64 or tuple(out.shape) != (B, 4) or not out.is_contiguous() or out.device != node1.device:
+        raise EmcidHipError(f"score_chains_pair: out must be a contiguous ({B}, 4) f64 tensor on {node1.device}")
+    _check(load().emcid_score_chains_pair_f64(
+        _ptr(node1, torch.float64, "node1"), node1.shape[0], _ptr(anc1, torch.int32, "anc1"), anc1.stride(0),
+        _ptr(depth1, torch.int32, "depth1"), _ptr(end_node1, torch.int64, "end_node1"),
+        _ptr(node2, torch.float64, "node2"), node2.shape[0], _ptr(anc2, torch.int32, "anc2"), anc2.stride(0),
+        _ptr(depth2, torch.int32, "depth2"), _ptr(end_node2, torch.int64, "end_node2"), B, _ptr(out, torch.float64, "out"),
+        _stream(node1)), "emcid_score_chains_pair_f64")
+    return out
+
+
+def score_pooled(a: torch.Tensor, b: torch.Tensor, ln: torch.nn.LayerNorm, proj_weight: torch.Tensor,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(rows, 4) f64 in HBM, one launch (emcid_score_pooled_f32): per row of the fp32 matrices ``a``, ``b`` (rows, cols), with
+    a^ = ln(a), b^ = ln(b) in fp64 (``ln``: an affine LayerNorm over cols) and P = ``proj_weight`` (proj, cols) fp32, a projection
+    without bias: ||P (a^ - b^)||^2, ||P b^||^2, ||P a^||^2, (P a^) . (P b^).  a^ - b^ is formed from a - b (``score_rows``):
+    identical rows give an exact 0 in slot 0.  Row strides may differ from cols (multiples of 4); cols % 4 == 0 and <= 2048, else
+    the library refuses the call before it launches anything."""
+    if a.dim() != 2 or a.shape != b.shape:
+        raise EmcidHipError(f"score_pooled: a, b must be matrices of one shape (got {tuple(a.shape)}, {tuple(b.shape)})")
+    rows, cols = a.shape
+    if proj_weight.dim() != 2 or proj_weight.shape[1] != cols or proj_weight.shape[0] < 1:
+        raise EmcidHipError(f"score_pooled: proj_weight must be a (proj, {cols}) matrix (got {tuple(proj_weight.shape)})")
+    for x, nm in ((a, "a"), (b, "b"), (proj_weight, "proj_weight")):
+        if x.stride(1) != 1 or x.device != a.device:
+            raise EmcidHipError(f"score_pooled: {nm} must have unit column stride and live on {a.device}")
+    if not isinstance(ln, torch.nn.LayerNorm) or ln.weight is None or ln.bias is None or tuple(ln.normalized_shape) != (cols,) \
+            or not ln.weight.is_contiguous() or not ln.bias.is_contiguous() or ln.weight.device != a.device:
+        raise EmcidHipError("score_pooled: a LayerNorm over the last dimension with contiguous affine parameters")
+    if out is None:
+        out = torch.empty(rows, 4, dtype=torch.float64, device=a.device)
+    if out.dtype != torch.float64 or tuple(out.shape) != (rows, 4) or not out.is_contiguous() or out.device != a.device:
+        raise EmcidHipError(f"score_pooled: out must be a contiguous ({rows}, 4) f64 tensor on {a.device}")
+    _check(load().emcid_score_pooled_f32(
+        _ptr(a, torch.float32, "a"), a.stride(0), _ptr(b, torch.float32, "b"), b.stride(0), _ptr(ln.weight, torch.float32, "gamma"),
+        _ptr(ln.bias, torch.float32, "beta"), float(ln.eps), _ptr(proj_weight, torch.float32, "proj_weight"), proj_weight.stride(0),
+        rows, cols, proj_weight.shape[0], _ptr(out, torch.float64, "out"), _stream(a)), "emcid_score_pooled_f32")
     return out
 
 

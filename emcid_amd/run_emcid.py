@@ -3,8 +3,9 @@
 Same instruction JSON (reference: test_examples/*.json) — ``requests``, ``hparams`` (name of ``{hparams_dir}/{name}.json``),
 ``model_ckpt`` ("sd-v1.4" | "sdxl-1.0"), ``mom2_weight``, ``edit_weight``, optional ``mom2_weight_2``, optional ``sweep`` (sd-v1.4:
 a list of [mom2_weight, edit_weight] pairs run over the requests in one ``sweep_emcid_text_encoder`` call), optional
-``holdout_prompts`` (sd-v1.4: a list of prompt strings; the edit is scored on them by ``emcid_main.EditScorer`` and the summary —
-median and largest ``left`` over the concepts, largest and median ``drift_max`` over the prompts — is printed, with a ``sweep`` one
+``holdout_prompts`` (a list of prompt strings; the edit is scored on them by ``emcid_main.EditScorer`` — sdxl-1.0: by
+``emcid_main.PairEditScorer`` — and the summary — median and largest ``left`` over the concepts, largest and median ``drift_max``
+over the prompts; for the pair also each encoder's median ``left`` and the largest pooled drift — is printed, with a ``sweep`` one
 line per pair); ``val_prompts``,
 ``out_dir`` and ``sample_num`` are read and ignored: the reference generates pre/post images with the diffusion pipeline
 around the edit, this driver runs the edit only, reports its wall clock like experiments/emcid_test.py:1171-1180 and
@@ -94,8 +95,6 @@ def run(instruction_path, device="cuda:0", pipe=None, pipe_kind="synthetic", hpa
         torch.cuda.synchronize()
     t0 = time.time()
     holdout = ins.get("holdout_prompts")
-    if holdout and ins["model_ckpt"] != "sd-v1.4":
-        raise ValueError('"holdout_prompts" is for model_ckpt sd-v1.4 (EditScorer scores one CLIP text encoder)')
     if ins.get("sweep"):
         from .nethook import get_parameter
         names = [f"{hparams.rewrite_module_tmp.format(l)}.weight" for l in hparams.layers]
@@ -124,10 +123,13 @@ def run(instruction_path, device="cuda:0", pipe=None, pipe_kind="synthetic", hpa
         if scorer is not None:
             print(f"edit score over {len(holdout)} holdout prompts: {json.dumps(scorer.score().summary())}")
     else:
+        scorer = em.PairEditScorer(pipe, ins["requests"], hparams, device, holdout=list(holdout), cache_name=cache_name) if holdout else None
         em.apply_emcid_to_sdxl_text_encoders(pipe, ins["requests"], hparams, device, mom2_weight=ins["mom2_weight"],
                                              mom2_weight_2=ins.get("mom2_weight_2", None), edit_weight=ins["edit_weight"],
                                              cache_name=cache_name, stat_dir=XL_STATS_DIR1 if stats_dir is None else stats_dir,
                                              stat_dir_2=XL_STATS_DIR2 if stats_dir_2 is None else stats_dir_2, verbose=verbose)
+        if scorer is not None:
+            print(f"edit score over {len(holdout)} holdout prompts: {json.dumps(scorer.score().summary())}")
     if device.startswith("cuda"):
         torch.cuda.synchronize()
     dt = time.time() - t0

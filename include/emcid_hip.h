@@ -538,11 +538,34 @@ int emcid_cov_factor_refactor_f64(void* cov_ws, int64_t workspace_bytes, int64_t
  *     out[p][0] = max r    out[p][1] = mean r    out[p][2] = r(e)    out[p][3] = chain position of the max (the first on a tie)
  * Chains of up to 128 nodes.  An end node or chain entry outside [0, U), or a chain longer than 128 or than ld_anc, reads
  * nothing: that prompt's four outputs are NaN.
+ *
+ * For a PAIR of encoders whose token states are concatenated (SDXL; emcid_main.PairEditScorer), two more, also added under ABI 16
+ * and with the same conventions (one launch, no workspace, no host synchronisation, fixed summation order):
+ *
+ * emcid_score_chains_pair_f64: emcid_score_chains_f64 over two independently numbered tries (node_e [U_e][8], anc_e [U_e][ld_anc_e],
+ * depth_e [U_e], end_e [B]).  With c_e = anc_e[end_e[p]][0 .. depth_e[end_e[p]]] the ratio at chain position j is
+ *     r_j = sqrt((node1[c_1[j]][0] + node2[c_2[j]][0]) / (node1[c_1[j]][1] + node2[c_2[j]][1]))        (0 when both sums are 0)
+ * and out[p][0..3] = max, mean, r at the end, chain position of the max (the first on a tie).  Chains of up to 128 nodes.  Chains
+ * of different lengths, an end node or chain entry outside [0, U_e), a chain longer than 128 or than ld_anc_e: that prompt's four
+ * outputs are NaN; every index is checked before the load it is used in.
+ *
+ * emcid_score_pooled_f32: per row r < rows of the fp32 matrices a [rows][lda], b [rows][ldb], with a^, b^ their LayerNorm in fp64
+ * (gamma, beta [cols] fp32, both required) and P [proj][ldp] fp32 a projection without bias, every value converted to fp64,
+ *     out[r][0] = ||P (a^ - b^)||^2    out[r][1] = ||P b^||^2    out[r][2] = ||P a^||^2    out[r][3] = (P a^) . (P b^)
+ * a^ - b^ is formed from a - b as in emcid_score_rows_f32 and P a^ as P (a^ - b^) + P b^: identical rows give exactly 0 in slot 0
+ * and the same bits in slots 1, 2 and 3.  A workgroup of eight waves normalises four rows into LDS (64 cols + 1024 bytes) and sweeps
+ * P once for them.  cols % 4 == 0, cols <= 2048, proj >= 1, leading dimensions multiples of 4 and >= cols, 16-byte aligned pointers;
+ * anything else is EMCID_ERR_BAD_ARG and nothing is launched.
  * ------------------------------------------------------------------------------------------- */
 int emcid_score_rows_f32(const float* a, int64_t lda, const float* b, int64_t ldb, const float* t, int64_t ldt, const float* gamma,
                          const float* beta, float eps, int64_t rows, int64_t cols, double* out, void* stream);
 int emcid_score_chains_f64(const double* node, int64_t U, const int32_t* anc, int64_t ld_anc, const int32_t* depth,
                            const int64_t* end_node, int64_t B, double* out, void* stream);
+int emcid_score_chains_pair_f64(const double* node1, int64_t U1, const int32_t* anc1, int64_t ld_anc1, const int32_t* depth1,
+                                const int64_t* end1, const double* node2, int64_t U2, const int32_t* anc2, int64_t ld_anc2,
+                                const int32_t* depth2, const int64_t* end2, int64_t B, double* out, void* stream);
+int emcid_score_pooled_f32(const float* a, int64_t lda, const float* b, int64_t ldb, const float* gamma, const float* beta, float eps,
+                           const float* P, int64_t ldp, int64_t rows, int64_t cols, int64_t proj, double* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Fallback with the reference's own solver semantics.  torch.linalg.solve (reference: emcid/emcid_main.py:1045-1048) is
