@@ -7,7 +7,9 @@ Public surface mirrors the reference's (SilentView/EMCID) for this path:
                            EditSession (a sequence of edits in which later ones preserve the keys of earlier ones),
                            EditScorer / EditScore / select_point (per-concept efficacy and held-out drift of an edit, read on
                            the device from the encoder's own output), PairEditScorer / PairEditScore (the same for the SDXL
-                           pair of encoders, read where an SDXL UNet is conditioned),
+                           pair of encoders, read where an SDXL UNet is conditioned), sweep_emcid_sdxl_text_encoders (a grid of
+                           (mom2_weight, mom2_weight_2, edit_weight) triples over the pair, each encoder walked over its own
+                           distinct points, every triple scored by one reduction on the device),
                            apply_emcid_to_cross_attn, execute_emcid_cross_attn (UNet cross-attention K/V)
     emcid_amd.uce_train    edit_text_encoder_uce, edit_model_uce (the UCE baseline's closed forms)
     emcid_amd.layer_stats  layer_stats_text_encoder (Stage 0)
@@ -24,7 +26,7 @@ def __getattr__(name):
     if name in ("apply_emcid_to_text_encoder", "apply_emcid_to_sdxl_text_encoders", "apply_emcid_to_model",
                 "execute_emcid_text_encoder", "execute_emcid_sd_xl_text_encoders", "get_cov_text_encoder",
                 "apply_emcid_to_cross_attn", "execute_emcid_cross_attn", "get_cov_cross_attn",
-                "sweep_emcid_text_encoder", "EditSession", "PreservedSetFull", "EditScorer", "EditScore", "select_point",
+                "sweep_emcid_text_encoder", "sweep_emcid_sdxl_text_encoders", "EditSession", "PreservedSetFull", "EditScorer", "EditScore", "select_point",
                 "PairEditScorer", "PairEditScore"):
         from . import emcid_main
         return getattr(emcid_main, name)

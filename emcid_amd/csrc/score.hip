@@ -5,6 +5,7 @@
 // Both follow add_layernorm_wave_kernel (attention.hip): one wave per row or prompt, four per workgroup, reductions by shuffles,
 // no LDS, no atomics, plain vector loads and stores.  For the SDXL pair of encoders (emcid_main.PairEditScorer):
 //   score_chains_pair_kernel  score_chains_kernel over the concatenated columns of two encoders, each with a trie of its own
+//   score_chains_pair_grid_kernel  score_chains_pair_kernel for every combination of a bank of node sums per encoder (a sweep)
 //   score_pooled_kernel       per row pair: the sums the relative distance of text_projection(final_layer_norm(.)) is made of;
 //                             four rows per workgroup, normalised once into LDS, for one sweep of the projection matrix
 #include "common.h"
@@ -297,6 +298,123 @@ __global__ __launch_bounds__(256) void score_chains_pair_kernel(const double* __
     }
 }
 
+constexpr int GRID_CHUNK = 16;       // combinations per blockIdx.y of score_chains_pair_grid_kernel
+constexpr int GRID_FLIGHT = 4;       // of them, those whose node sums are all loaded before the first is reduced
+
+// score_chains_pair_kernel for every combination c < C of a point of encoder 1 with a point of encoder 2 (a sweep over the pair,
+// emcid_main.sweep_emcid_sdxl_text_encoders): node_e is a BANK [G_e][U_e][8] of score_rows outputs, combo [C][2] names a bank
+// entry of each, and out[c][p][0..3] is what score_chains_pair_kernel writes for prompt p on those two entries — the same
+// operations in the same order, the same shuffle tree, the same tie rule: the same bits.  One wave per prompt, four per workgroup;
+// the prompt's two chains are read ONCE into registers (two indices per lane and trie) and judged once, then the wave walks
+// blockIdx.y's chunks of GRID_CHUNK combinations, GRID_FLIGHT at a time: their loads are all issued before the first reduction.
+// A prompt score_chains_pair_kernel refuses gets four NaN in every combination, a combination with an entry outside [0, G1) x
+// [0, G2) four NaN for every prompt; every index is checked before the load it is used in.
+__global__ __launch_bounds__(256) void score_chains_pair_grid_kernel(
+    const double* __restrict__ node1, int64_t G1, int64_t U1, const int32_t* __restrict__ anc1, int64_t ld_anc1,
+    const int32_t* __restrict__ depth1, const int64_t* __restrict__ end1, const double* __restrict__ node2, int64_t G2, int64_t U2,
+    const int32_t* __restrict__ anc2, int64_t ld_anc2, const int32_t* __restrict__ depth2, const int64_t* __restrict__ end2, int B,
+    const int32_t* __restrict__ combo, int64_t C, double* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (p >= B) return;
+    const int64_t e1 = end1[p], e2 = end2[p];
+    const bool e_ok = e1 >= 0 && e1 < U1 && e2 >= 0 && e2 < U2;
+    const int n = e_ok ? depth1[e1] + 1 : 0, n2 = e_ok ? depth2[e2] + 1 : 0;
+    bool ok = e_ok && n == n2 && n >= 1 && n <= 128 && n <= ld_anc1 && n <= ld_anc2;
+    int64_t u1[2] = {0, 0}, u2[2] = {0, 0};        // the lane's two chain positions in each trie
+    bool take[2] = {false, false};
+    if (ok) {
+        const int32_t* c1 = anc1 + e1 * ld_anc1;
+        const int32_t* c2 = anc2 + e2 * ld_anc2;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int pos = lane + 64 * j;
+            if (pos < n) {
+                const int64_t a = c1[pos], b = c2[pos];
+                if (a < 0 || a >= U1 || b < 0 || b >= U2) {
+                    ok = false;
+                } else {
+                    u1[j] = a;
+                    u2[j] = b;
+                    take[j] = true;
+                }
+            }
+        }
+    }
+    const int bad = __any(!ok);
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const int64_t n_chunks = (C + GRID_CHUNK - 1) / GRID_CHUNK;
+    for (int64_t chunk = blockIdx.y; chunk < n_chunks; chunk += gridDim.y) {
+        const int64_t c_end = (chunk + 1) * GRID_CHUNK < C ? (chunk + 1) * GRID_CHUNK : C;
+        for (int64_t c0 = chunk * GRID_CHUNK; c0 < c_end; c0 += GRID_FLIGHT) {
+            double2 v1[GRID_FLIGHT][2], v2[GRID_FLIGHT][2];
+            bool live[GRID_FLIGHT];        // (the same in every lane: the combination's entries and the prompt's verdict)
+#pragma unroll
+            for (int k = 0; k < GRID_FLIGHT; ++k) {
+                live[k] = false;
+                if (c0 + k < c_end) {
+                    const int64_t g1 = combo[2 * (c0 + k)], g2 = combo[2 * (c0 + k) + 1];
+                    live[k] = !bad && g1 >= 0 && g1 < G1 && g2 >= 0 && g2 < G2;
+                    if (live[k]) {
+                        const double* b1 = node1 + g1 * U1 * 8;
+                        const double* b2 = node2 + g2 * U2 * 8;
+#pragma unroll
+                        for (int j = 0; j < 2; ++j) {
+                            if (take[j]) {
+                                v1[k][j] = *reinterpret_cast<const double2*>(b1 + u1[j] * 8);
+                                v2[k][j] = *reinterpret_cast<const double2*>(b2 + u2[j] * 8);
+                            }
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < GRID_FLIGHT; ++k) {
+                if (c0 + k >= c_end) break;
+                double2* o = reinterpret_cast<double2*>(out + ((c0 + k) * B + p) * 4);
+                if (!live[k]) {
+                    if (lane == 0) {
+                        o[0] = make_double2(nan, nan);
+                        o[1] = make_double2(nan, nan);
+                    }
+                    continue;
+                }
+                double best = -1.0, sum = 0.0, last = 0.0;
+                int best_pos = 1 << 30;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const int pos = lane + 64 * j;
+                    if (take[j]) {
+                        const double num = v1[k][j].x + v2[k][j].x, den = v1[k][j].y + v2[k][j].y;
+                        const double r = (num == 0.0 && den == 0.0) ? 0.0 : sqrt(num / den);
+                        sum += r;
+                        if (r > best) {
+                            best = r;
+                            best_pos = pos;
+                        }
+                        if (pos == n - 1) last = r;
+                    }
+                }
+#pragma unroll
+                for (int s = 32; s > 0; s >>= 1) {
+                    sum += __shfl_xor(sum, s, 64);
+                    last += __shfl_xor(last, s, 64);
+                    const double ob = __shfl_xor(best, s, 64);
+                    const int op = __shfl_xor(best_pos, s, 64);
+                    if (ob > best || (ob == best && op < best_pos)) {
+                        best = ob;
+                        best_pos = op;
+                    }
+                }
+                if (lane == 0) {
+                    o[0] = make_double2(best, sum / (double)n);
+                    o[1] = make_double2(last, (double)best_pos);
+                }
+            }
+        }
+    }
+}
+
 constexpr int POOLED_ROWS = 4;       // rows per workgroup: all four per sweep of P
 constexpr int POOLED_WAVES = 8;      // waves per workgroup: the first four normalise a row each, all eight sweep P
 
@@ -502,6 +620,25 @@ int emcid_score_chains_pair_f64(const double* node1, int64_t U1, const int32_t* 
     ScopedProf sp(KC_MISC, (hipStream_t)stream);
     hipLaunchKernelGGL(score_chains_pair_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, node1, U1, anc1,
                        ld_anc1, depth1, end1, node2, U2, anc2, ld_anc2, depth2, end2, (int)B, out);
+    EMCID_CHECK_LAUNCH();
+    return EMCID_OK;
+}
+
+int emcid_score_chains_pair_grid_f64(const double* node1, int64_t G1, int64_t U1, const int32_t* anc1, int64_t ld_anc1,
+                                     const int32_t* depth1, const int64_t* end1, const double* node2, int64_t G2, int64_t U2,
+                                     const int32_t* anc2, int64_t ld_anc2, const int32_t* depth2, const int64_t* end2, int64_t B,
+                                     const int32_t* combo, int64_t C, double* out, void* stream) {
+    EMCID_CHECK_ARG(node1 && anc1 && depth1 && end1 && node2 && anc2 && depth2 && end2 && combo && out);
+    EMCID_CHECK_ARG(G1 > 0 && G1 < (1LL << 31) && G2 > 0 && G2 < (1LL << 31) && C > 0 && C < (1LL << 31));
+    EMCID_CHECK_ARG(U1 > 0 && U1 < (1LL << 31) && U2 > 0 && U2 < (1LL << 31) && ld_anc1 > 0 && ld_anc2 > 0 && B > 0 && B < (1LL << 31));
+    // (the kernel's offsets are 64-bit: a bank of G U 8 doubles and the C B 4 outputs must be addressable)
+    EMCID_CHECK_ARG(G1 <= (1LL << 58) / U1 && G2 <= (1LL << 58) / U2 && C <= (1LL << 58) / B);
+    EMCID_CHECK_ARG(aligned16(node1) && aligned16(node2) && aligned16(out));
+    const int64_t n_chunks = (C + GRID_CHUNK - 1) / GRID_CHUNK;
+    ScopedProf sp(KC_MISC, (hipStream_t)stream);
+    hipLaunchKernelGGL(score_chains_pair_grid_kernel, dim3((unsigned)((B + 3) / 4), (unsigned)(n_chunks < 65535 ? n_chunks : 65535)),
+                       dim3(256), 0, (hipStream_t)stream, node1, G1, U1, anc1, ld_anc1, depth1, end1, node2, G2, U2, anc2, ld_anc2,
+                       depth2, end2, (int)B, combo, C, out);
     EMCID_CHECK_LAUNCH();
     return EMCID_OK;
 }

@@ -962,6 +962,117 @@ def _sweep_unit_factors(plan: EncoderEditPlan, dev) -> Optional[hip.CovFactors]:
     return unit
 
 
+def validate_pair_grid(grid) -> List[tuple]:
+    """``grid`` as a list of (mom2_update_weight, mom2_update_weight_2, edit_weight) float triples for the SDXL pair of encoders,
+    or ValueError: ``validate_grid``'s refusals per component — empty, an entry that is not a triple (a pair included), a
+    mom2_update_weight of either encoder <= 0 or not finite, edit_weight outside (0, 1)."""
+    try:
+        pts = [(float(p[0]), float(p[1]), float(p[2])) for p in grid] if all(len(p) == 3 for p in grid) else None
+    except (TypeError, ValueError, IndexError) as e:
+        raise ValueError(f"grid must be a sequence of (mom2_weight, mom2_weight_2, edit_weight) triples: {e}") from e
+    if pts is None:
+        raise ValueError("grid must be a sequence of (mom2_weight, mom2_weight_2, edit_weight) triples")
+    if not pts:
+        raise ValueError("grid is empty")
+    for lam1, lam2, e in pts:
+        validate_grid([(lam1, e), (lam2, e)])
+    return pts
+
+
+def pair_grid_plan(triples):
+    """(pts1, pts2, combos) of a validated grid of triples: the two encoders are independent models, so TE1's weights depend on
+    (lam1, e) alone and TE2's on (lam2, e).  ``pts1``: the distinct (lam1, e) in order of first appearance, ``pts2``: the distinct
+    (lam2, e); ``combos[g]`` = (index in pts1, index in pts2) of triple g.  Host only."""
+    pts1, pts2, combos = [], [], []
+    seen1, seen2 = {}, {}
+    for lam1, lam2, e in triples:
+        i = seen1.setdefault((lam1, e), len(pts1))
+        if i == len(pts1):
+            pts1.append((lam1, e))
+        j = seen2.setdefault((lam2, e), len(pts2))
+        if j == len(pts2):
+            pts2.append((lam2, e))
+        combos.append((i, j))
+    return pts1, pts2, combos
+
+
+class SweepWalk:
+    """The points of a sweep over ONE prepared plan, one at a time (``run_sweep`` is a loop over this; a sweep over the SDXL pair
+    steps two of them side by side).
+
+        with SweepWalk(plan) as walk:            # the shared part: solver form, the state entering the first edited layer,
+            edits = walk.point(lam, e)           # chol(C) at unit scale; then per point: rescale, run, check, LU rerun if need be
+            ...                                  # the point's weights are in place; ``edits`` are its LayerEdits (dW per layer)
+            plan.restore_weights()               # before the next point
+                                                 # on exit, also by an exception: weights, lam, edit_weight, solver put back
+
+    ``point`` returns the LayerEdits of the run whose weights are in place — those of the LU rerun when the point took it.  It
+    counts LAST_PATHS sweep_points / sweep_cov_factorizations / sweep_prefix_runs up; whoever walks resets them."""
+
+    def __init__(self, plan: EncoderEditPlan):
+        if plan.chunk is None or plan.graph is None:
+            raise clip_forward.UnsupportedEncoder("run_sweep replays the prefix-trie forward's state")
+        self.plan, self.saved = plan, (plan.lam, plan.edit_weight, plan.solver)
+        self.unit = self.scaled = self.state = self.form = self.pinned = None
+
+    def __enter__(self):
+        plan, LP = self.plan, clip_forward.LAST_PATHS
+        ch, first_edit = plan.chunk, plan.layers[0]
+        w0 = get_parameter(plan.text_encoder, plan.weight_name(first_edit))
+        dev, d = w0.device, w0.shape[1]
+        try:
+            with phase("sweep: shared"), torch.no_grad():
+                form = solver_form(plan, d, False)          # once: N, d and the shard decide, not the pair
+                pinned = "dual" if form in DUAL_FORMS else form if form == "lu" else "direct"
+                self.state = ch.state if ch.state is not None and ch.state[0] == first_edit else \
+                    (first_edit,) + tuple(clip_forward.run_prefix(plan.graph, ch.trie, first_edit))
+                LP["sweep_prefix_runs"] += 1
+                self.unit = _sweep_unit_factors(plan, dev) if form in DUAL_FORMS else None
+                if form in DUAL_FORMS and self.unit is None:
+                    # C itself has a non-positive pivot: so has a C for every pair.  Every point is a single call's fallback.
+                    logging.getLogger("emcid_amd").warning("the statistics are not positive definite: every point of the sweep runs "
+                                                           "on the pivoted-LU solver")
+                    if os.environ.get("EMCID_LU_FALLBACK", "1") == "0":
+                        raise FloatingPointError("the statistics are not positive definite (non-positive pivot in chol(C))")
+                    pinned = "lu"
+                self.form, self.pinned = form, pinned
+        except BaseException:
+            self.close()
+            raise
+        return self
+
+    def point(self, lam: float, e: float) -> List[LayerEdit]:
+        plan, LP = self.plan, clip_forward.LAST_PATHS
+        with phase("sweep: points"):
+            plan.lam, plan.edit_weight, plan.solver = lam, e, self.pinned
+            if self.unit is not None:
+                self.scaled = hip.cov_factor_rescale(self.unit, 2.0 * lam * (1.0 - e), self.scaled, lam=lam, edit_weight=e)
+                plan.sweep_factors = self.scaled
+            elif self.pinned == "lu" and self.form != "lu":
+                LP["lu_fallbacks"] = LP.get("lu_fallbacks", 0) + 1
+            plan.chunk.state = self.state
+            edits = run_encoder_edit(plan)
+            try:
+                check_info(plan)
+            except FloatingPointError as err:
+                plan.sweep_factors = None
+                plan.chunk.state = self.state
+                edits = rerun_with_lu(plan, err)
+            LP["sweep_points"] += 1
+        return edits
+
+    def close(self):
+        plan = self.plan
+        plan.restore_weights()
+        plan.lam, plan.edit_weight, plan.solver = self.saved
+        plan.sweep_factors = plan.cov_factors = None
+        plan.chunk.state = None
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
 def run_sweep(plan: EncoderEditPlan, grid, visit=None) -> list:
     """Stage 2 of ONE prepared plan at every (mom2_update_weight, edit_weight) pair of ``grid``, in order.  While a point's edited
     weights are in place ``visit(index, (lam, e))`` is called; its return values are the result.  The weights are back at their
@@ -971,58 +1082,21 @@ def run_sweep(plan: EncoderEditPlan, grid, visit=None) -> list:
     launched by prepare, replayed: run_layers_from only reads it), the choice of the solver, and one factorization of the statistics
     at unit scale — a point rescales it into its own workspace (hip.cov_factor_rescale) and then runs the chain of a single call on
     warm factors: run_layers_from, the fused edit-layer call, check_info, rerun_with_lu for a point whose Cholesky reports a pivot
-    (that point only).  LAST_PATHS gauges of the last sweep: sweep_points, sweep_cov_factorizations (len(layers) for a dual form
-    on a cold cache, 0 on cached unit factors or for the direct form, which assembles A from C itself), sweep_prefix_runs (1)."""
+    (that point only).  The per-point body is ``SweepWalk``.  LAST_PATHS gauges of the last sweep: sweep_points,
+    sweep_cov_factorizations (len(layers) for a dual form on a cold cache, 0 on cached unit factors or for the direct form, which
+    assembles A from C itself), sweep_prefix_runs (1)."""
     pts = validate_grid(grid)
-    if plan.chunk is None or plan.graph is None:
-        raise clip_forward.UnsupportedEncoder("run_sweep replays the prefix-trie forward's state")
+    walk = SweepWalk(plan)
     LP = clip_forward.LAST_PATHS
     LP["sweep_points"] = LP["sweep_cov_factorizations"] = LP["sweep_prefix_runs"] = 0
-    ch, first_edit = plan.chunk, plan.layers[0]
-    w0 = get_parameter(plan.text_encoder, plan.weight_name(first_edit))
-    dev, d = w0.device, w0.shape[1]
-    saved = (plan.lam, plan.edit_weight, plan.solver)
+    for key in ("sweep_pair_points_1", "sweep_pair_points_2", "sweep_pair_combos"):      # (a pair sweep's gauges: not of this sweep)
+        LP.pop(key, None)
     results = []
-    try:
-        with phase("sweep: shared"), torch.no_grad():
-            form = solver_form(plan, d, False)          # once: N, d and the shard decide, not the pair
-            pinned = "dual" if form in DUAL_FORMS else form if form == "lu" else "direct"
-            state = ch.state if ch.state is not None and ch.state[0] == first_edit else \
-                (first_edit,) + tuple(clip_forward.run_prefix(plan.graph, ch.trie, first_edit))
-            LP["sweep_prefix_runs"] += 1
-            unit = _sweep_unit_factors(plan, dev) if form in DUAL_FORMS else None
-            if form in DUAL_FORMS and unit is None:
-                # C itself has a non-positive pivot: so has a C for every pair.  Every point is a single call's fallback.
-                logging.getLogger("emcid_amd").warning("the statistics are not positive definite: every point of the sweep runs "
-                                                       "on the pivoted-LU solver")
-                if os.environ.get("EMCID_LU_FALLBACK", "1") == "0":
-                    raise FloatingPointError("the statistics are not positive definite (non-positive pivot in chol(C))")
-                pinned = "lu"
-        scaled = None
+    with walk:
         for index, (lam, e) in enumerate(pts):
-            with phase("sweep: points"):
-                plan.lam, plan.edit_weight, plan.solver = lam, e, pinned
-                if unit is not None:
-                    scaled = hip.cov_factor_rescale(unit, 2.0 * lam * (1.0 - e), scaled, lam=lam, edit_weight=e)
-                    plan.sweep_factors = scaled
-                elif pinned == "lu" and form != "lu":
-                    LP["lu_fallbacks"] = LP.get("lu_fallbacks", 0) + 1
-                ch.state = state
-                run_encoder_edit(plan)
-                try:
-                    check_info(plan)
-                except FloatingPointError as err:
-                    plan.sweep_factors = None
-                    ch.state = state
-                    rerun_with_lu(plan, err)
-                LP["sweep_points"] += 1
+            walk.point(lam, e)
             results.append(visit(index, (lam, e)) if visit is not None else None)
             plan.restore_weights()
-    finally:
-        plan.restore_weights()
-        plan.lam, plan.edit_weight, plan.solver = saved
-        plan.sweep_factors = plan.cov_factors = None
-        ch.state = None
     return results
 
 

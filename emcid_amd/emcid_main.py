@@ -1865,11 +1865,12 @@ class _PairEncoder:
     """One encoder of a ``PairEditScorer``: what ``EditScorer`` keeps of its one encoder, with the holdout read one layer earlier
     (``hidden_states[-2]``, raw) and, ``pooled``, the last layer continued on the EOS rows."""
 
-    def __init__(self, te, graph, layers, plan, ids_h, eos_h, pooled: bool):
+    def __init__(self, te, graph, layers, plan, ids_h, eos_h, pooled: bool, keep_state: bool = False):
         self.te, self.graph, self.layers, self.pooled = te, graph, layers, pooled
         self.chunk, self.zs = plan.chunk, plan.resolve_targets()
         self._state = tuple(plan.chunk.state[1:])
-        plan.chunk.state = None
+        if not keep_state:          # (a sweep's own plan: its points replay the state as well)
+            plan.chunk.state = None
         dev = self.zs.device
         self.trie_h = clip_forward.build_trie(ids_h, eos_h, dev)
         self._state_h = tuple(clip_forward.run_prefix(graph, self.trie_h, layers[0]))
@@ -1953,11 +1954,18 @@ class PairEditScorer:
     take — not HF CLIP, not fp32 in HBM, fewer than two layers, h % 4 != 0 or h > 2048, a ``text_projection`` with a bias —, a
     holdout prompt of more than ``SCORE_MAX_CHAIN`` tokens (``clip_forward.UnsupportedEncoder``); a missing v* file
     (``FileNotFoundError``); and, as in ``EditScorer``, a ``score()`` when a parameter of either encoder other than its edited fc2
-    weights is not the tensor, at the address, with the version counter it had at construction (``ValueError``).  Not done here:
-    an SDXL sweep, sessions, sharded calls, the hooked-HF forward, positions behind the EOS."""
+    weights is not the tensor, at the address, with the version counter it had at construction (``ValueError``).
 
-    def __init__(self, pipe, requests: List[Dict], hparams: EMCIDXLHyperParams, device: Optional[str] = None, holdout=None,
-                 cache_name: Optional[str] = None, shard=None):
+    A grid of (mom2_weight, mom2_weight_2, edit_weight) triples is ``sweep_emcid_sdxl_text_encoders``: with ``score=`` it builds
+    one scorer on its own prepared plans and reads every triple through ``score_points`` — each encoder's half of ``score()``
+    (``_half``: the one statement of it) once per DISTINCT point of that encoder, one ``hip.score_chains_pair_grid`` for all the
+    triples' pair drifts, one pinned read.  Not done here: sessions, sharded calls, the hooked-HF forward, positions behind the
+    EOS."""
+
+    @staticmethod
+    def _host_checks(pipe, requests, hparams, device, holdout, shard):
+        """Every refusal of the constructor that needs neither a launch nor a file, and what it found on the way: (holdout, per
+        encoder (te, tok, layers, v* suffix, graph, h, holdout ids, EOS positions), text_projection | None, TE2's final LayerNorm)."""
         if not isinstance(hparams, EMCIDXLHyperParams):
             raise TypeError(f"hparams must be EMCIDXLHyperParams, got {type(hparams).__name__}")
         if getattr(pipe, "text_encoder_2", None) is None or getattr(pipe, "tokenizer_2", None) is None:
@@ -2015,23 +2023,34 @@ class PairEditScorer:
                     and ln2.weight.is_cuda and ln2.weight.dtype == torch.float32 and tuple(ln2.normalized_shape) == (h2,)):
                 raise clip_forward.UnsupportedEncoder("the pooled readout takes text_projection as an fp32 nn.Linear without bias over an "
                                                       f"affine fp32 final LayerNorm of h = {h2} columns")
+        return holdout, found, proj, ln2
+
+    def __init__(self, pipe, requests: List[Dict], hparams: EMCIDXLHyperParams, device: Optional[str] = None, holdout=None,
+                 cache_name: Optional[str] = None, shard=None, _plans=None, _checked=None):
+        # ``_plans`` (sweep_emcid_sdxl_text_encoders): the sweep's own prepared plans of these very requests — their tries, v* rows
+        # (read, or computed by Stage 1, the way a call does) and the states their prefix runs left, which the sweep's points replay
+        # as well; ``_checked``: what the sweep's own call of ``_host_checks`` returned before it prepared them
+        holdout, found, proj, ln2 = _checked if _checked is not None else self._host_checks(pipe, requests, hparams, device, holdout, shard)
+        layer_tmp = hparams.layer_module_tmp
         for te, tok, layers, suffix, graph, h, ids_h, eos_h in found:
-            if _any_vstar_missing(requests, hparams, cache_name, suffix):
+            if _plans is None and _any_vstar_missing(requests, hparams, cache_name, suffix):
                 raise FileNotFoundError(f"a v* file (suffix {suffix!r}) of the {len(requests)} requests is missing under {cache_name!r}: "
                                         f"a PairEditScorer reads the targets an edit was made towards and never runs Stage 1")
         self.pipe, self.hparams, self.holdout, self.proj, self.ln2 = pipe, hparams, holdout, proj, ln2
         self.sources = score_row_sources(requests, 1)
         self.encoders = []
         with torch.no_grad():
-            for (te, tok, layers, suffix, graph, h, ids_h, eos_h), lam in zip(found, (hparams.mom2_update_weight, hparams.mom2_update_weight_2)):
-                plan = prepare_encoder_edit(
+            for i, ((te, tok, layers, suffix, graph, h, ids_h, eos_h), lam) in enumerate(zip(found, (hparams.mom2_update_weight,
+                                                                                                     hparams.mom2_update_weight_2))):
+                plan = _plans[i] if _plans is not None else prepare_encoder_edit(
                     te, tok, requests, layers, hparams.rewrite_module_tmp, float(lam), float(hparams.edit_weight),
                     lambda suffix=suffix, h=h: load_v_stars(requests, hparams, cache_name, suffix, None, width=h, pin=True),
                     lambda: {}, ConceptShard(), layer_module_tmp=layer_tmp, num_edit_tokens=1)
                 if plan.chunk is None or plan.graph is not graph or plan.chunk.state is None or plan.chunk.state[0] != layers[0] \
                         or plan.layers != layers:
                     raise clip_forward.UnsupportedEncoder("the requests did not take the prefix-trie forward")
-                self.encoders.append(_PairEncoder(te, graph, layers, plan, ids_h, eos_h, pooled=proj is not None and suffix == "_2"))
+                self.encoders.append(_PairEncoder(te, graph, layers, plan, ids_h, eos_h, pooled=proj is not None and suffix == "_2",
+                                                  keep_state=_plans is not None))
         e1, e2 = self.encoders
         n1, n2, B = e1.Z0.shape[0], e2.Z0.shape[0], len(holdout)
         if n1 != len(self.sources) or n2 != len(self.sources):
@@ -2044,8 +2063,7 @@ class PairEditScorer:
     def _part(self, buf, i, width):
         return buf[self._cuts[i]:self._cuts[i + 1]].view(-1, width)
 
-    def score(self) -> PairEditScore:
-        """Score the weights of both encoders as they are against the baseline of construction (class docstring)."""
+    def _check_frozen(self):
         for which, enc in enumerate(self.encoders, 1):
             now = enc.signature()
             if now != enc.frozen:
@@ -2054,38 +2072,95 @@ class PairEditScorer:
                 raise ValueError(f"parameters of text encoder {which} other than the edited fc2 weights changed since this "
                                  f"PairEditScorer was built ({', '.join(moved[:4]) or 'the parameter list'}"
                                  f"{', ...' if len(moved) > 4 else ''}): its kept states are no longer this encoder's; build a new one")
+
+    def _half(self, i, rows, node, chains, pooled=None):
+        """Encoder i's half of a score on its weights as they are, issued on the current stream: its replay, ``score_rows`` into
+        ``rows`` (N, 8) and into ``node`` (holdout nodes, 8), ``score_chains`` into ``chains`` (B, 4) and, for TE2 with a
+        projection, ``score_pooled`` into ``pooled`` (B, 4)."""
+        enc = self.encoders[i]
+        Z, H, h_last = enc.forward()
+        hip.score_rows(Z, enc.Z0, t=enc.zs, out=rows)
+        hip.score_rows(H, enc.H0, out=node)
+        hip.score_chains(node, enc.trie_h.anc, enc.trie_h.depth, enc.trie_h.lookup_node, out=chains)
+        if enc.pooled:
+            hip.score_pooled(h_last, enc.H0last, self.ln2, self.proj.weight, out=pooled)
+
+    def _encoder_score(self, rows, chains) -> EditScore:
+        """The ``EditScore`` of one encoder from its (N, 8) row sums and (B, 4) chain values on the host."""
+        tiny = torch.finfo(torch.float64).tiny
+        moved2, resid2, resid02, dot = rows[:, 0], rows[:, 4], rows[:, 5], rows[:, 6]
+        left = torch.where(resid02 > 0, (resid2 / resid02.clamp(min=tiny)).sqrt(), torch.zeros_like(resid2))
+        den = (moved2 * resid02).sqrt()
+        cos = torch.where(den > 0, dot / den.clamp(min=tiny), torch.zeros_like(dot))
+        return EditScore(self.sources, left, cos, resid2.sqrt(), resid02.sqrt(), self.holdout, chains[:, 0].clone(),
+                         chains[:, 1].clone(), chains[:, 2].clone(), chains[:, 3].clone())
+
+    @staticmethod
+    def _pooled_drift(sums):
+        tiny = torch.finfo(torch.float64).tiny
+        return torch.where(sums[:, 0] > 0, (sums[:, 0] / sums[:, 1].clamp(min=tiny)).sqrt(), torch.zeros_like(sums[:, 0]))
+
+    def score(self) -> PairEditScore:
+        """Score the weights of both encoders as they are against the baseline of construction (class docstring)."""
+        self._check_frozen()
         e1, e2 = self.encoders
         out = self._out
         with torch.no_grad():
             for i, enc in enumerate(self.encoders):
-                Z, H, h_last = enc.forward()
-                hip.score_rows(Z, enc.Z0, t=enc.zs, out=self._part(out, i, 8))
-                hip.score_rows(H, enc.H0, out=enc.node)
-                hip.score_chains(enc.node, enc.trie_h.anc, enc.trie_h.depth, enc.trie_h.lookup_node, out=self._part(out, 2 + i, 4))
+                self._half(i, self._part(out, i, 8), enc.node, self._part(out, 2 + i, 4), self._part(out, 5, 4) if enc.pooled else None)
             hip.score_chains_pair(e1.node, e1.trie_h.anc, e1.trie_h.depth, e1.trie_h.lookup_node,
                                   e2.node, e2.trie_h.anc, e2.trie_h.depth, e2.trie_h.lookup_node, out=self._part(out, 4, 4))
-            if self.proj is not None:
-                hip.score_pooled(h_last, e2.H0last, self.ln2, self.proj.weight, out=self._part(out, 5, 4))
             self._host.copy_(out, non_blocking=True)
             torch.cuda.current_stream(out.device).synchronize()
         host = self._host.clone()
-        tiny = torch.finfo(torch.float64).tiny
+        pair = self._part(host, 4, 4)
+        pooled = self._pooled_drift(self._part(host, 5, 4)) if self.proj is not None else None
+        return PairEditScore(self._encoder_score(self._part(host, 0, 8), self._part(host, 2, 4)),
+                             self._encoder_score(self._part(host, 1, 8), self._part(host, 3, 4)), self.holdout, pair[:, 0].clone(),
+                             pair[:, 1].clone(), pair[:, 2].clone(), pair[:, 3].clone(), pooled)
 
-        def encoder_score(i):
-            rows, chains = self._part(host, i, 8), self._part(host, 2 + i, 4)
-            moved2, resid2, resid02, dot = rows[:, 0], rows[:, 4], rows[:, 5], rows[:, 6]
-            left = torch.where(resid02 > 0, (resid2 / resid02.clamp(min=tiny)).sqrt(), torch.zeros_like(resid2))
-            den = (moved2 * resid02).sqrt()
-            cos = torch.where(den > 0, dot / den.clamp(min=tiny), torch.zeros_like(dot))
-            return EditScore(self.sources, left, cos, resid2.sqrt(), resid02.sqrt(), self.holdout, chains[:, 0].clone(),
-                             chains[:, 1].clone(), chains[:, 2].clone(), chains[:, 3].clone())
+    def score_points(self, n1: int, n2: int, combos, place) -> List[PairEditScore]:
+        """The factorised readout of a sweep (``sweep_emcid_sdxl_text_encoders``): ``with place(i, g):`` holds point g < n1 / n2 of
+        encoder i = 0 / 1 in place; inside, that encoder's half of a score runs into the point's slot of one output buffer and of
+        the encoder's bank of node sums — TE1 over all its points, then TE2 over its own.  Then ONE
+        ``hip.score_chains_pair_grid`` over ``combos`` [(point of TE1, point of TE2)] and ONE pinned read: one ``PairEditScore``
+        per combination — ``te1`` from its TE1 point, ``te2`` and ``drift_pooled`` from its TE2 point, the pair drift from the
+        grid kernel."""
+        self._check_frozen()
+        e1, e2 = self.encoders
+        N, B, C = len(self.sources), len(self.holdout), len(combos)
+        dev = e1.Z0.device
+        per = [N * 8 + B * 4, N * 8 + B * 4 + (B * 4 if self.proj is not None else 0)]
+        cuts = [0, n1 * per[0], n1 * per[0] + n2 * per[1]]
+        out = torch.empty(cuts[2] + C * B * 4, dtype=torch.float64, device=dev)
+        host = torch.empty(out.numel(), dtype=torch.float64, pin_memory=True)
+        banks = [torch.empty(n, enc.H0.shape[0], 8, dtype=torch.float64, device=dev) for n, enc in ((n1, e1), (n2, e2))]
+        combo = torch.tensor([list(c) for c in combos], dtype=torch.int32).reshape(C, 2).to(dev)
 
-        pair, pooled = self._part(host, 4, 4), None
-        if self.proj is not None:
-            sums = self._part(host, 5, 4)
-            pooled = torch.where(sums[:, 0] > 0, (sums[:, 0] / sums[:, 1].clamp(min=tiny)).sqrt(), torch.zeros_like(sums[:, 0]))
-        return PairEditScore(encoder_score(0), encoder_score(1), self.holdout, pair[:, 0].clone(), pair[:, 1].clone(),
-                             pair[:, 2].clone(), pair[:, 3].clone(), pooled)
+        def slot(buf, i, g):
+            s = buf[cuts[i] + g * per[i]:cuts[i] + (g + 1) * per[i]]
+            return s[:N * 8].view(N, 8), s[N * 8:N * 8 + B * 4].view(B, 4), s[N * 8 + B * 4:].view(-1, 4)
+
+        with torch.no_grad():
+            for i, n in enumerate((n1, n2)):
+                for g in range(n):
+                    with place(i, g):
+                        rows, chains, pooled = slot(out, i, g)
+                        self._half(i, rows, banks[i][g], chains, pooled if self.encoders[i].pooled else None)
+            hip.score_chains_pair_grid(banks[0], e1.trie_h.anc, e1.trie_h.depth, e1.trie_h.lookup_node,
+                                       banks[1], e2.trie_h.anc, e2.trie_h.depth, e2.trie_h.lookup_node, combo,
+                                       out=out[cuts[2]:].view(C, B, 4))
+            host.copy_(out, non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()
+        halves = [[slot(host, i, g) for g in range(n)] for i, n in ((0, n1), (1, n2))]
+        pair = host[cuts[2]:].view(C, B, 4)
+        scores = []
+        for c, (g1, g2) in enumerate(combos):
+            (r1, c1, _), (r2, c2, p2) = halves[0][g1], halves[1][g2]
+            scores.append(PairEditScore(self._encoder_score(r1, c1), self._encoder_score(r2, c2), self.holdout, pair[c, :, 0].clone(),
+                                        pair[c, :, 1].clone(), pair[c, :, 2].clone(), pair[c, :, 3].clone(),
+                                        self._pooled_drift(p2) if self.proj is not None else None))
+        return scores
 
 
 def sweep_emcid_text_encoder(pipe, requests: List[Dict], hparams: EMCIDHyperParams, grid, device: Optional[str] = None,
@@ -2522,6 +2597,161 @@ def apply_emcid_to_sdxl_text_encoders(pipe, requests: List[Dict], hparams: EMCID
     if verbose:
         print(f"New weights successfully inserted into {[e.weight_name for e in e1 + e2]}")
     return pipe, o1, o2
+
+
+def sweep_emcid_sdxl_text_encoders(pipe, requests: List[Dict], hparams: EMCIDXLHyperParams, grid, device: Optional[str] = None,
+                                   visit=None, score=None, cache_name: Optional[str] = None, stat_dir=XL_STATS_DIR1,
+                                   stat_dir_2=XL_STATS_DIR2, shard=None, stage1=None, verbose: bool = False) -> list:
+    """One request set at every (mom2_weight, mom2_weight_2, edit_weight) triple of ``grid`` on the SDXL PAIR of text encoders, in
+    ONE call: ``sweep_emcid_text_encoder`` for the pair.  At a triple TE1 holds W + dW(mom2_weight, edit_weight) and TE2 holds what
+    ``apply_emcid_to_sdxl_text_encoders`` leaves, W + 2 dW(mom2_weight_2, edit_weight) while ``SDXL_TE2_DOUBLE_APPLY`` holds (W + dW
+    otherwise).  The preparation is a call's (``_sdxl_plans``: tokenization, tries, the unedited leading layers, the v* reads, Stage
+    1 on a cache miss), made once; each encoder's statistics are factored once (``edit_engine.SweepWalk``); ``hparams`` is NOT
+    mutated; on return — also when ``visit`` raises — both encoders hold their original weights.  Invalid grids raise ValueError
+    first (``edit_engine.validate_pair_grid``).
+
+    The two encoders are independent models: TE1's weights and everything read of them depend on (mom2_weight, edit_weight) alone,
+    TE2's on (mom2_weight_2, edit_weight); only the pair drift couples them, and it is a function of the per-node sums each
+    encoder's readout leaves (``PairEditScorer``).  ``edit_engine.pair_grid_plan`` gives the distinct points of each encoder.
+
+    ``score=[holdout prompt strings]`` with ``visit=None`` — the factorised path: a ``PairEditScorer`` is built once on the two
+    prepared plans (nothing is tokenized, read or run twice), TE1 is walked over ITS distinct points and TE2 over its own — a 4 x 4
+    cross of the two mom2 weights at one edit_weight is 4 + 4 encoder edits and replays, not 2 x 16 —, each point's half of a
+    score runs into its slot of a bank of node sums, then ONE ``hip.score_chains_pair_grid`` launch reduces every triple's pair
+    drift and ONE pinned read brings everything to the host (``PairEditScorer.score_points``).  The result is one ``PairEditScore``
+    per triple, in grid order; ``select_point`` takes the list.
+
+    With a ``visit`` — the joint path: the triples are walked in grid order and ``visit(triple, pipe)`` is called while BOTH
+    encoders hold the triple's weights; an encoder whose own point equals the previous triple's is not edited again.  The result
+    per triple is ``visit``'s return value, or ``(visit(...), PairEditScore)`` with ``score=``.  ``visit=None, score=None``
+    collects ``({weight name: edited fc2 weight of TE1}, {the same of TE2})``, fp32 on the host, per triple.
+
+    A point whose Cholesky reports a non-positive pivot is rerun alone on the pivoted LU (TE2's second apply then adds the rerun's
+    own dW).  A stale-cache verdict (``_retry_if_stale``) puts both encoders back and redoes the sweep once from its first point.
+    Refused before anything is launched: what ``PairEditScorer`` and ``_sdxl_plans`` refuse; ``score=`` on a collective shard
+    (``ValueError``) or on an encoder the prefix-trie forward does not take (``UnsupportedEncoder``).  Without ``score=`` such an
+    encoder gets one ordinary call per triple (counted by ``clip_forward.note_fallback``).
+
+    LAST_PATHS gauges of the last sweep: sweep_pair_points_1, sweep_pair_points_2 (encoder edits run; on the fallback one per
+    triple each), sweep_pair_combos (triples), and ``run_sweep``'s own, summed over both encoders.  Unlike every other gauge the
+    three ``sweep_pair_*`` keys are NOT always in ``LAST_PATHS``: they are set by this function and taken out again by the next
+    ``sweep_emcid_text_encoder`` (``edit_engine.run_sweep``), whose gauges are all the ``sweep_*`` keys of the last sweep — read
+    them with ``LAST_PATHS.get(key)`` unless a pair sweep has just run.
+
+    ``PairEditScorer.score_points`` allocates its output buffer, its pinned host buffer and the two banks of node sums per call
+    (their sizes follow the grid, not the scorer); ``score()`` keeps its own preallocated pair."""
+    import contextlib
+    from .edit_engine import SweepWalk, pair_grid_plan, validate_pair_grid
+    triples = validate_pair_grid(grid)
+    if not isinstance(hparams, EMCIDXLHyperParams):
+        raise TypeError(f"hparams must be EMCIDXLHyperParams, got {type(hparams).__name__}")
+    if getattr(pipe, "text_encoder_2", None) is None or getattr(pipe, "tokenizer_2", None) is None:
+        raise ValueError("sweep_emcid_sdxl_text_encoders sweeps the SDXL pair: the pipe has no text_encoder_2 / tokenizer_2")
+    hp = deepcopy(hparams)
+    hp.mom2_update_weight, hp.mom2_update_weight_2, hp.edit_weight = triples[0]
+    if hp.num_edit_tokens != 1:
+        raise AssertionError("num_edit_tokens should be 1")   # (as _sdxl_plans, reference :1246)
+    for te in (pipe.text_encoder, pipe.text_encoder_2):
+        if device is not None and torch.device(device) != next(te.parameters()).device:
+            raise ValueError(f"a text encoder is on {next(te.parameters()).device}, not on {device}")
+    pts = pair_grid_plan(triples)
+    checked = None
+    if score is not None:       # every host-side refusal of a scorer, before the preparation launches anything
+        if _shard_from_env(shard).collective:
+            raise ValueError("score= runs on one rank: a collective ConceptShard is not supported")
+        score = list(score)
+        if not score or not all(isinstance(p, str) for p in score):
+            raise ValueError("score= takes the holdout: a non-empty list of prompt strings")
+        checked = PairEditScorer._host_checks(pipe, requests, hp, device, score, shard)
+    names = [[f"{hp.rewrite_module_tmp.format(l)}.weight" for l in layers] for layers in (hp.layers, hp.layers_2)]
+    encoders = (pipe.text_encoder, pipe.text_encoder_2)
+    LP = clip_forward.LAST_PATHS
+    scorer = None
+
+    def second_apply(edits):
+        if SDXL_TE2_DOUBLE_APPLY:   # execute left TE2 edited, apply adds the update once more (:93-99)
+            for e in edits:
+                _axpy_weight_(nethook.get_parameter(pipe.text_encoder_2, e.weight_name), e.dW)
+
+    def collect(triple):
+        if scorer is not None:
+            return (visit(triple, pipe), scorer.score())
+        if visit is not None:
+            return visit(triple, pipe)
+        return tuple({n: nethook.get_parameter(te, n).detach().to("cpu", torch.float32).clone() for n in ns}
+                     for te, ns in zip(encoders, names))
+
+    _announce(requests, verbose)
+    stage1 = _default_stage1_sdxl(pipe, hp, stage1)
+    for attempt in (0, 1):
+        plans = _sdxl_plans(pipe, requests, hp, cache_name, stat_dir, stat_dir_2, verbose, shard, stage1)
+        if any(p.chunk is None or p.graph is None for p in plans):
+            if score is not None:
+                raise clip_forward.UnsupportedEncoder("score= needs the prefix-trie forward, which an encoder or the request set did not take")
+            break
+        LP["sweep_points"] = LP["sweep_cov_factorizations"] = LP["sweep_prefix_runs"] = 0
+        LP["sweep_pair_points_1"] = LP["sweep_pair_points_2"] = 0
+        LP["sweep_pair_combos"] = len(triples)
+        try:
+            if score is not None:
+                # on the sweep's own plans, before the first point, on the original weights; again after a stale-cache retry
+                scorer = PairEditScorer(pipe, requests, hp, device, holdout=score, cache_name=cache_name, shard=shard, _plans=plans,
+                                        _checked=checked)
+            with SweepWalk(plans[0]) as w1, SweepWalk(plans[1]) as w2:
+                walks = (w1, w2)
+
+                def put(i, point):
+                    edits = walks[i].point(*point)
+                    if i == 1:
+                        second_apply(edits)
+                    LP[f"sweep_pair_points_{i + 1}"] += 1
+
+                if scorer is not None and visit is None:
+                    @contextlib.contextmanager
+                    def place(i, g):
+                        put(i, pts[i][g])
+                        try:
+                            yield
+                        finally:
+                            plans[i].restore_weights()
+
+                    return scorer.score_points(len(pts[0]), len(pts[1]), pts[2], place)
+                results, held = [], [None, None]
+                for triple, combo in zip(triples, pts[2]):
+                    for i in (0, 1):
+                        if held[i] != combo[i]:       # (an encoder whose own point is the previous triple's stays as it is)
+                            if held[i] is not None:
+                                plans[i].restore_weights()
+                            held[i] = None
+                            put(i, pts[i][combo[i]])
+                            held[i] = combo[i]
+                    results.append(collect(triple))
+                return results
+        except clip_forward.StaleWeightCacheError as e:
+            # (as _retry_if_stale: the engine put the stale encoder's weights back, the walks' exit the other's; a multi-rank job raises)
+            import torch.distributed as dist
+            if attempt or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+                raise
+            _note_stale("sweep_emcid_sdxl_text_encoders", e, "sweep")
+            if score is not None:       # (the dropped caches took the encoders' graphs with them: the scorer's checks name the new ones)
+                checked = PairEditScorer._host_checks(pipe, requests, hp, device, score, shard)
+    # the hooked-HF forward has no stored state to replay: one ordinary call per triple, both encoders restored after each
+    clip_forward.note_fallback("sweep_emcid_sdxl_text_encoders", clip_forward.UnsupportedEncoder("no prefix-trie forward: one call per triple"))
+    LP["sweep_pair_points_1"] = LP["sweep_pair_points_2"] = LP["sweep_pair_combos"] = len(triples)      # (every triple edits both)
+    results = []
+    for index, triple in enumerate(triples):
+        if index:         # (the plans prepared above are the first triple's)
+            hp_i = deepcopy(hparams)
+            hp_i.mom2_update_weight, hp_i.mom2_update_weight_2, hp_i.edit_weight = triple
+            plans = _sdxl_plans(pipe, requests, hp_i, cache_name, stat_dir, stat_dir_2, verbose, shard, stage1)
+        try:
+            run_checked(plans[0], keep_factors=False, restore=False)
+            second_apply(run_checked(plans[1], keep_factors=False, restore=False))
+            results.append(collect(triple))
+        finally:
+            plans[0].restore_weights()
+            plans[1].restore_weights()
+    return results
 
 
 # ---- edited-weight export (the reference never saves its edits; SURVEY.md §8f-2) --------------------------------

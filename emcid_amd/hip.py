@@ -34,6 +34,7 @@ EXPORTS = [
     "emcid_cov_factor_fold_workspace_bytes", "emcid_cov_factor_fold_f64",
     "emcid_session_refold_update_f64", "emcid_cov_factor_refactor_f64",
     "emcid_score_rows_f32", "emcid_score_chains_f64", "emcid_score_chains_pair_f64", "emcid_score_pooled_f32",
+    "emcid_score_chains_pair_grid_f64",
     "emcid_edit_lu_workspace_bytes", "emcid_edit_layer_lu_f64", "emcid_lu_solve_f64",
     "emcid_edit_dual_cols_stage1_f64", "emcid_edit_dual_s", "emcid_edit_dual_u", "emcid_edit_dual_cols_stage2_f64",
     "emcid_apply_update2d_f32", "emcid_linear_f32", "emcid_linear_ws_f32", "emcid_linear_workspace_bytes",
@@ -116,6 +117,7 @@ def load():
         "emcid_score_rows_f32": (i32, [p, i64, p, i64, p, i64, p, p, f32, i64, i64, p, p]),
         "emcid_score_chains_f64": (i32, [p, i64, p, i64, p, p, i64, p, p]),
         "emcid_score_chains_pair_f64": (i32, [p, i64, p, i64, p, p, p, i64, p, i64, p, p, i64, p, p]),
+        "emcid_score_chains_pair_grid_f64": (i32, [p, i64, i64, p, i64, p, p, p, i64, i64, p, i64, p, p, i64, p, i64, p, p]),
         "emcid_score_pooled_f32": (i32, [p, i64, p, i64, p, p, f32, p, i64, i64, i64, i64, p, p]),
         "emcid_cholesky_solve_f64": (i32, [p, i64, i64, p, p, p, i64, i64, p]),
         "emcid_edit_dual_cols_stage1_f64": (i32, [p, p, p, i64, i64, i64, f64, i32, f64, p, i64, i64, p, i32, p, i64, p]),
@@ -1713,6 +1715,42 @@ def score_chains_pair(node1: torch.Tensor, anc1: torch.Tensor, depth1: torch.Ten
         _ptr(node2, torch.float64, "node2"), node2.shape[0], _ptr(anc2, torch.int32, "anc2"), anc2.stride(0),
         _ptr(depth2, torch.int32, "depth2"), _ptr(end_node2, torch.int64, "end_node2"), B, _ptr(out, torch.float64, "out"),
         _stream(node1)), "emcid_score_chains_pair_f64")
+    return out
+
+
+def score_chains_pair_grid(node1_bank: torch.Tensor, anc1: torch.Tensor, depth1: torch.Tensor, end_node1: torch.Tensor,
+                           node2_bank: torch.Tensor, anc2: torch.Tensor, depth2: torch.Tensor, end_node2: torch.Tensor,
+                           combo: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(C, B, 4) f64 in HBM, one launch (emcid_score_chains_pair_grid_f64): ``score_chains_pair`` for every row (g1, g2) of
+    ``combo`` (C, 2) int32 on the device, on ``node1_bank[g1]`` and ``node2_bank[g2]`` — the banks are (G_e, U_e, 8) f64, one
+    ``score_rows`` result per point of encoder e.  ``out[c]`` holds the bits ``score_chains_pair`` gives on those two slices; a
+    row of ``combo`` that leaves a bank gives NaN for every prompt of that combination."""
+    for bank, nm in ((node1_bank, "node1_bank"), (node2_bank, "node2_bank")):
+        if bank.dim() != 3 or bank.shape[0] < 1:
+            raise EmcidHipError(f"score_chains_pair_grid: {nm} must be a (G, U, 8) f64 tensor (got {tuple(bank.shape)})")
+    _check_chain_arrays("score_chains_pair_grid", node1_bank[0], anc1, depth1, end_node1)
+    _check_chain_arrays("score_chains_pair_grid", node2_bank[0], anc2, depth2, end_node2)
+    if not node1_bank.is_contiguous() or not node2_bank.is_contiguous():
+        raise EmcidHipError("score_chains_pair_grid: the banks must be contiguous")
+    B = end_node1.numel()
+    if end_node2.numel() != B:
+        raise EmcidHipError(f"score_chains_pair_grid: {B} end nodes in the first trie, {end_node2.numel()} in the second")
+    if combo.dim() != 2 or combo.shape[1] != 2 or combo.shape[0] < 1 or not combo.is_contiguous():
+        raise EmcidHipError(f"score_chains_pair_grid: combo must be a non-empty contiguous (C, 2) int32 tensor (got {tuple(combo.shape)})")
+    if any(x.device != node1_bank.device for x in (anc1, depth1, end_node1, node2_bank, anc2, depth2, end_node2, combo)):
+        raise EmcidHipError(f"score_chains_pair_grid: every operand must live on {node1_bank.device}")
+    n_combo = combo.shape[0]
+    if out is None:
+        out = torch.empty(n_combo, B, 4, dtype=torch.float64, device=node1_bank.device)
+    if out.dtype != torch.float64 or tuple(out.shape) != (n_combo, B, 4) or not out.is_contiguous() or out.device != node1_bank.device:
+        raise EmcidHipError(f"score_chains_pair_grid: out must be a contiguous ({n_combo}, {B}, 4) f64 tensor on {node1_bank.device}")
+    _check(load().emcid_score_chains_pair_grid_f64(
+        _ptr(node1_bank, torch.float64, "node1_bank"), node1_bank.shape[0], node1_bank.shape[1], _ptr(anc1, torch.int32, "anc1"),
+        anc1.stride(0), _ptr(depth1, torch.int32, "depth1"), _ptr(end_node1, torch.int64, "end_node1"),
+        _ptr(node2_bank, torch.float64, "node2_bank"), node2_bank.shape[0], node2_bank.shape[1], _ptr(anc2, torch.int32, "anc2"),
+        anc2.stride(0), _ptr(depth2, torch.int32, "depth2"), _ptr(end_node2, torch.int64, "end_node2"), B,
+        _ptr(combo, torch.int32, "combo"), n_combo, _ptr(out, torch.float64, "out"), _stream(node1_bank)),
+        "emcid_score_chains_pair_grid_f64")
     return out
 
 

@@ -2,11 +2,12 @@
 
 Same instruction JSON (reference: test_examples/*.json) — ``requests``, ``hparams`` (name of ``{hparams_dir}/{name}.json``),
 ``model_ckpt`` ("sd-v1.4" | "sdxl-1.0"), ``mom2_weight``, ``edit_weight``, optional ``mom2_weight_2``, optional ``sweep`` (sd-v1.4:
-a list of [mom2_weight, edit_weight] pairs run over the requests in one ``sweep_emcid_text_encoder`` call), optional
+a list of [mom2_weight, edit_weight] pairs run over the requests in one ``sweep_emcid_text_encoder`` call; sdxl-1.0: a list of
+[mom2_weight, mom2_weight_2, edit_weight] triples run over the pair in one ``sweep_emcid_sdxl_text_encoders`` call), optional
 ``holdout_prompts`` (a list of prompt strings; the edit is scored on them by ``emcid_main.EditScorer`` — sdxl-1.0: by
 ``emcid_main.PairEditScorer`` — and the summary — median and largest ``left`` over the concepts, largest and median ``drift_max``
 over the prompts; for the pair also each encoder's median ``left`` and the largest pooled drift — is printed, with a ``sweep`` one
-line per pair); ``val_prompts``,
+line per pair or triple); ``val_prompts``,
 ``out_dir`` and ``sample_num`` are read and ignored: the reference generates pre/post images with the diffusion pipeline
 around the edit, this driver runs the edit only, reports its wall clock like experiments/emcid_test.py:1171-1180 and
 writes the edited fc2 matrices to a safetensors file.
@@ -49,10 +50,9 @@ def load_instruction(path, hparams_dir=HPARAMS_DIR):
     else:
         raise ValueError("Invalid model_ckpt")
     if "sweep" in ins:
-        from .edit_engine import validate_grid
-        if ckpt != "sd-v1.4":
-            raise ValueError('"sweep" is for model_ckpt sd-v1.4 (sweep_emcid_text_encoder)')
-        ins["sweep"] = validate_grid(ins["sweep"])
+        from .edit_engine import validate_grid, validate_pair_grid
+        # sd-v1.4: [mom2_weight, edit_weight] pairs; sdxl-1.0: [mom2_weight, mom2_weight_2, edit_weight] triples
+        ins["sweep"] = validate_grid(ins["sweep"]) if ckpt == "sd-v1.4" else validate_pair_grid(ins["sweep"])
     hparams = set_weights(cls.from_json(Path(hparams_dir) / f"{ins['hparams']}.json"), ins["mom2_weight"], ins["edit_weight"])
     return ins, hparams, f"cache/{ins['hparams']}/"
 
@@ -84,8 +84,9 @@ def build_pipe(kind: str, model_ckpt: str, device: str):
 
 def run(instruction_path, device="cuda:0", pipe=None, pipe_kind="synthetic", hparams_dir=HPARAMS_DIR, cache_name: Optional[str] = None,
         stats_dir=None, stats_dir_2=None, out: Optional[str] = None, verbose=True):
-    """Apply the instruction's edit; returns (pipe, hparams, seconds).  An instruction with a ``sweep`` list runs every pair of it
-    over the requests instead (the encoder is left unedited): per point the report of ``sweep_report``, printed and — ``out`` —
+    """Apply the instruction's edit; returns (pipe, hparams, seconds).  For sdxl-1.0 a ``sweep`` list holds triples, and with
+    ``holdout_prompts`` the score summary of every triple is printed, one JSON line each.  An instruction with a ``sweep`` list
+    runs every pair or triple of it over the requests instead (the encoder is left unedited): per point the report of ``sweep_report``, printed and — ``out`` —
     written as JSON; returns (pipe, hparams, seconds, reports)."""
     from . import emcid_main as em
     ins, hparams, default_cache = load_instruction(instruction_path, hparams_dir)
@@ -95,6 +96,39 @@ def run(instruction_path, device="cuda:0", pipe=None, pipe_kind="synthetic", hpa
         torch.cuda.synchronize()
     t0 = time.time()
     holdout = ins.get("holdout_prompts")
+    if ins.get("sweep") and ins["model_ckpt"] == "sdxl-1.0":
+        kw = dict(cache_name=cache_name, stat_dir=XL_STATS_DIR1 if stats_dir is None else stats_dir,
+                  stat_dir_2=XL_STATS_DIR2 if stats_dir_2 is None else stats_dir_2, verbose=verbose)
+        head = [dict(mom2_weight=t[0], mom2_weight_2=t[1], edit_weight=t[2]) for t in ins["sweep"]]
+        if holdout:     # the factorised path: one PairEditScore per triple, no weight leaves the device
+            scores = em.sweep_emcid_sdxl_text_encoders(pipe, ins["requests"], hparams, ins["sweep"], device, score=list(holdout), **kw)
+            reports = [dict(h, score=s.summary()) for h, s in zip(head, scores)]
+        else:           # per triple and encoder the figures of ``sweep_report``
+            from .nethook import get_parameter
+            encoders = (("layers", pipe.text_encoder, hparams.layers), ("layers_2", pipe.text_encoder_2, hparams.layers_2))
+            w0 = {key: {n: get_parameter(te, n).detach().clone() for n in (f"{hparams.rewrite_module_tmp.format(l)}.weight" for l in ls)}
+                  for key, te, ls in encoders}
+
+            def report(triple, p):
+                rec = {}
+                for key, te, _ in encoders:
+                    dws = {n: get_parameter(te, n).detach() - w for n, w in w0[key].items()}
+                    rec[key] = {n: {"dw_maxabs": float(dw.abs().max()), "dw_fro": float(dw.norm())} for n, dw in dws.items()}
+                return rec
+
+            recs = em.sweep_emcid_sdxl_text_encoders(pipe, ins["requests"], hparams, ins["sweep"], device, visit=report, **kw)
+            reports = [dict(h, **rec) for h, rec in zip(head, recs)]
+        if device.startswith("cuda"):
+            torch.cuda.synchronize()
+        dt = time.time() - t0
+        if verbose:
+            print(f"sweep of {len(reports)} triples takes {dt} seconds ({1e3 * dt / len(reports):.1f} ms per triple).")
+        if verbose or holdout:
+            for rec in reports:
+                print(json.dumps(rec))
+        if out:
+            Path(out).write_text(json.dumps(reports, indent=1))
+        return pipe, hparams, dt, reports
     if ins.get("sweep"):
         from .nethook import get_parameter
         names = [f"{hparams.rewrite_module_tmp.format(l)}.weight" for l in hparams.layers]

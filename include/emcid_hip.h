@@ -549,6 +549,16 @@ int emcid_cov_factor_refactor_f64(void* cov_ws, int64_t workspace_bytes, int64_t
  * of different lengths, an end node or chain entry outside [0, U_e), a chain longer than 128 or than ld_anc_e: that prompt's four
  * outputs are NaN; every index is checked before the load it is used in.
  *
+ * emcid_score_chains_pair_grid_f64 (a sweep over the pair, emcid_main.sweep_emcid_sdxl_text_encoders; added under ABI 16 as well):
+ * emcid_score_chains_pair_f64 for C combinations of a point of encoder 1 with a point of encoder 2 in one launch.  node_e is a
+ * bank [G_e][U_e][8] f64, one emcid_score_rows_f32 output per point of that encoder; combo [C][2] int32 ON THE DEVICE names a
+ * bank entry of each; out [C][B][4] f64, and out[c][p][0..3] is exactly what emcid_score_chains_pair_f64 writes for prompt p given
+ * node1 + combo[c][0] U1 8 and node2 + combo[c][1] U2 8: the same operations in the same order, the same bits.  The chains of a
+ * prompt are read once for all combinations.  A combo entry outside [0, G1) x [0, G2): four NaN for every prompt of that
+ * combination; a prompt emcid_score_chains_pair_f64 gives NaN: four NaN in every combination; every index is checked before the
+ * load it is used in.  A null pointer, G_e, U_e, B or C < 1 (or >= 2^31), a bank or out that is not 16-byte aligned:
+ * EMCID_ERR_BAD_ARG and nothing is launched.
+ *
  * emcid_score_pooled_f32: per row r < rows of the fp32 matrices a [rows][lda], b [rows][ldb], with a^, b^ their LayerNorm in fp64
  * (gamma, beta [cols] fp32, both required) and P [proj][ldp] fp32 a projection without bias, every value converted to fp64,
  *     out[r][0] = ||P (a^ - b^)||^2    out[r][1] = ||P b^||^2    out[r][2] = ||P a^||^2    out[r][3] = (P a^) . (P b^)
@@ -564,6 +574,10 @@ int emcid_score_chains_f64(const double* node, int64_t U, const int32_t* anc, in
 int emcid_score_chains_pair_f64(const double* node1, int64_t U1, const int32_t* anc1, int64_t ld_anc1, const int32_t* depth1,
                                 const int64_t* end1, const double* node2, int64_t U2, const int32_t* anc2, int64_t ld_anc2,
                                 const int32_t* depth2, const int64_t* end2, int64_t B, double* out, void* stream);
+int emcid_score_chains_pair_grid_f64(const double* node1, int64_t G1, int64_t U1, const int32_t* anc1, int64_t ld_anc1,
+                                     const int32_t* depth1, const int64_t* end1, const double* node2, int64_t G2, int64_t U2,
+                                     const int32_t* anc2, int64_t ld_anc2, const int32_t* depth2, const int64_t* end2, int64_t B,
+                                     const int32_t* combo, int64_t C, double* out, void* stream);
 int emcid_score_pooled_f32(const float* a, int64_t lda, const float* b, int64_t ldb, const float* gamma, const float* beta, float eps,
                            const float* P, int64_t ldp, int64_t rows, int64_t cols, int64_t proj, double* out, void* stream);
 
