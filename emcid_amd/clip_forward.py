@@ -44,13 +44,16 @@ SPLIT_GEMM = os.environ.get("EMCID_SPLIT_GEMM", "1") != "0"
 # last sweep_emcid_text_encoder (edit_engine.run_sweep): its points, the covariance factorizations it ran, its prefix runs.
 # session_*: gauges of the last EditSession step (emcid_main.EditSession): its steps so far and preserved concept rows; its folds
 # and the rows they took into the session's base factor; the rows its retain lists added (EditSession.retain), folded ones included.
+# session_rescales: hip.session_rescale calls of the session so far (rescale, reweight, the points of a sweep; one per edited layer);
+# session_sweep_points: the points the last EditSession.sweep ran.
 # score_replays: replays of the trie forward made by an emcid_main.EditScorer (its construction and every score()).
 # sweep_pair_points_1, sweep_pair_points_2, sweep_pair_combos: present while the last sweep was a sweep_emcid_sdxl_text_encoders —
 # the encoder edits it ran on TE1 and on TE2, and its triples; edit_engine.run_sweep takes them out again.
 LAST_PATHS = {"linear_sp16": 0, "linear_f32": 0, "linear_torch": 0, "native_layers": 0, "fused_edit_layers": 0, "forward_trie": 0,
               "forward_hf": 0, "forward_hf_fallback": 0, "sweep_points": 0, "sweep_cov_factorizations": 0, "sweep_prefix_runs": 0,
               "session_steps": 0, "session_preserved_rows": 0, "session_folds": 0, "session_folded_rows": 0,
-              "session_retained_rows": 0, "session_released_rows": 0, "score_replays": 0}
+              "session_retained_rows": 0, "session_released_rows": 0, "score_replays": 0,
+              "session_rescales": 0, "session_sweep_points": 0}
 _FALLBACK_SEEN = set()
 
 

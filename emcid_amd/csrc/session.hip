@@ -58,6 +58,26 @@ __global__ __launch_bounds__(256) void gather_rows_f64_kernel(const double* __re
     for (int c = threadIdx.x; c < dp / 2; c += 256) o[c] = s ? s[c] : make_double2(0.0, 0.0);
 }
 
+// dst[j][0:dp] = factors[first + j] * src[first + j][0:dp] for j < n, zero for the padding rows n <= j < gridDim.x
+// (emcid_session_rescale_f64: the rows behind `first`, scaled through the workspace because with src == Yp they overlap their
+// destination).  One workgroup per row, double2, one multiply per element; src, dst 16-byte aligned, lds_ and dp even.
+__global__ __launch_bounds__(256) void scale_rows_f64_kernel(const double* __restrict__ src, int64_t lds_, const double* __restrict__ factors,
+                                                              int first, int n, double* __restrict__ dst, int dp) {
+    const int j = blockIdx.x;
+    const double f = j < n ? factors[first + j] : 0.0;
+    const double2* s = j < n ? reinterpret_cast<const double2*>(src + (int64_t)(first + j) * lds_) : nullptr;
+    double2* o = reinterpret_cast<double2*>(dst + (int64_t)j * dp);
+    for (int c = threadIdx.x; c < dp / 2; c += 256) {
+        double2 v = make_double2(0.0, 0.0);
+        if (s) {
+            v = s[c];
+            v.x *= f;
+            v.y *= f;
+        }
+        o[c] = v;
+    }
+}
+
 // ---- dual solver with a preserved key set (edit sessions) ---------------------------------------------------------------------
 // State of a layer: Yp [M, dp] (the Yt rows of every earlier step), Lp = chol(I + Yp Yp^T) [M, M], and the inverses of Lp's
 // 128 x 128 diagonal tiles (they keep the two solves against Lp GEMM-shaped).  A step appends N rows to all three.
@@ -508,6 +528,30 @@ int emcid_session_release_f64(const int32_t* keep_dev, int64_t n_keep, int64_t f
     hipStream_t st = (hipStream_t)stream;
     double* base = (double*)workspace;
     hipLaunchKernelGGL(gather_rows_f64_kernel, dim3((unsigned)ws.Np), dim3(256), 0, st, Yp, ldy, keep_dev + first, (int)N, (int)M,
+                       base + ws.off_Y, (int)ws.dp);
+    return session_append_rows(ws.key_half(base), N, Yp, ldy, Lp, ldl, tile_inv, first, info_dev, st, __func__);
+}
+
+/* ---- edit sessions: RESCALE rows of the preserved set ----------------------------------------------------------------------------
+ * Row i of the state becomes factors[i] * row i of src_Yp for first <= i < M (src_Yp may be Yp itself, or a copy of it: a sweep
+ * scales out of a backup into the live state); factors[i] == 1 below `first` is the caller's word and nothing below it is read or
+ * written.  A new (lam, edit_weight) multiplies every row by sqrt(a / a'), a = 2 lam (1 - e): chol(a' C) = sqrt(a' / a) chol(a C);
+ * a new weight of a concept multiplies its rows by sqrt(w' / w).  Lp and the tile inverses behind `first` are stale either way:
+ * the scaled rows go through the workspace's Yt block and re-enter as the key half of a step with M = first, N = M - first, as a
+ * release's kept rows do — no forward, no X, no statistics, no weights. */
+int emcid_session_rescale_f64(const double* factors_dev, const double* src_Yp, int64_t lds, int64_t first, int64_t d, double* Yp,
+                              int64_t ldy, double* Lp, int64_t ldl, double* tile_inv, int64_t capacity, int64_t M, void* workspace,
+                              int64_t workspace_bytes, int* info_dev, void* stream) {
+    EMCID_CHECK_ARG(factors_dev && src_Yp && d > 0 && Yp && Lp && tile_inv && workspace && aligned16(workspace) && info_dev);
+    EMCID_CHECK_ARG(0 <= first && first < M && M <= capacity);
+    const int64_t N = M - first;
+    EMCID_CHECK_ARG(session_state_ok(first, N, d, Yp, ldy, Lp, ldl, tile_inv, capacity));
+    EMCID_CHECK_ARG(aligned16(src_Yp) && lds >= round_up(d, NB) && lds % 2 == 0);
+    RetainWorkspace ws(N, d, capacity);
+    EMCID_CHECK_WORKSPACE(workspace_bytes, ws.total * (int64_t)sizeof(double), "");
+    hipStream_t st = (hipStream_t)stream;
+    double* base = (double*)workspace;
+    hipLaunchKernelGGL(scale_rows_f64_kernel, dim3((unsigned)ws.Np), dim3(256), 0, st, src_Yp, lds, factors_dev, (int)first, (int)N,
                        base + ws.off_Y, (int)ws.dp);
     return session_append_rows(ws.key_half(base), N, Yp, ldy, Lp, ldl, tile_inv, first, info_dev, st, __func__);
 }

@@ -22,6 +22,7 @@ otherwise.
 """
 import functools
 import logging
+import math
 import os
 import time
 from copy import deepcopy
@@ -816,6 +817,10 @@ class EditSession:
         sess.report()                             # report=True: what the last step did to the preserved keys and left of its residuals
         sess.release(sources)                     # take the rows of these request["source"] names out of the set again
         sess.rows(); sess.sources()               # the ledger: (source, "edit" | "retain", ordinal, token) per row; what release() can take
+        sess.rescale(mom2_weight, edit_weight)    # the session's lam / edit_weight from now on; held rows keep their committed scale
+        sess.apply(requests, point=(lam, e))      # ... rescale and step as ONE operation: a failed step takes the rescale back
+        sess.reweight(sources, weight)            # these concepts count from now on like keys retained now at `weight`
+        sess.sweep(requests, grid, scorer=...)    # trial steps at every (lam, e) of grid, nothing committed -> select_point
         sess.fold()                               # take the M preserved rows into the session's own base factor: M -> 0
         sess.folded                               # rows folded so far (still preserved, exactly)
         sess.folded_sources()                     # keep_folded=True: the names release() can take back out of the folds
@@ -882,6 +887,22 @@ class EditSession:
     (DESIGN.md §3).  Cost of the archive: folded x dp doubles per edited layer — 45 MB per layer per full fold (1 843 rows) at
     d = 3 072 — held until ``reset()`` / ``restore()``, which drop it.  The default (``False``) allocates and launches what it did.
 
+    RESCALE / REWEIGHT / SWEEP change how strongly the session edits and holds, from evidence.  The held rows live in factor
+    coordinates Yp = P L_s^-T, L_s = chol(lam C'); with a = 2 lam (1 - e) the base term is a C and chol(a' C) = sqrt(a' / a) chol(a C),
+    so another (lam', e') multiplies every row of Yp by rho = sqrt(a / a') and another weight w' of a concept held at w multiplies its
+    rows by sqrt(w' / w); Lp = chol(I + Yp Yp^T) and the tile inverses behind the first changed row are rebuilt by the key half a
+    release runs (``hip.session_rescale``: one scaling pass, then B, Lkp, T, its Cholesky, the append) — no forward, no X, no
+    statistics, no weight read or written.  ``rescale`` keeps P (a held row keeps the raw scale it was committed with; only the base
+    term moves) and re-points the factors later steps, ``fold()`` and ``save`` refer to at those of the new point, from the factor
+    cache as a step takes them; the scalar cannot reproduce the fp32 rounding of C (1 - e) / 0.5 (the reference's C'), an offset far
+    below the bar, and with e unchanged it is exact.  ``reweight`` takes its factors from the host ``row_scale``.
+    Both are atomic like ``release`` (copy, all layers, ONE pinned flag read, commit or put back and ``torch.linalg.LinAlgError``).
+    ``sweep`` prepares the requests once, copies the held state once, and per pair scales the live state out of the copy, runs the
+    step's chain on one unit factorization rescaled to the pair (``hip.cov_factor_rescale``), fills the pair's entry
+    (``EditScorer.score()``, ``report()``, ``visit``) and puts the weights back; in a ``finally`` the state goes back byte for byte.
+    All three refuse a session that has folded (its base a C + Pf^T Pf is a sum no scalar rescales), a collective shard and
+    EMCID_SOLVER=direct|lu before anything is launched or allocated.
+
     SAVE / LOAD carry a session across processes.  ``save(path)`` writes the fixed set-up, counters and ledgers, the COMMITTED rows
     of every layer without their padding or anything of the capacity (``hip.PreservedKeys.state_dict``: Yp[:M, :d], Lp[:M, :M], the
     tile inverses rows < M touch), the edited weights as they are and as they were before the first step, ``base`` of a folded
@@ -904,8 +925,8 @@ class EditSession:
     ``device``: as in apply_emcid_to_text_encoder; the state lives on the encoder's own device, ``device`` is only checked against it.
     ``capacity``: the largest M + N (default floor(0.6 d), the engine's dual / direct threshold); a step past it raises
     ``PreservedSetFull`` before anything is launched (with ``on_full="fold"``: only a step that exceeds it by itself).
-    mom2_update_weight, edit_weight and layers are fixed at construction
-    (``hparams`` may be mutated afterwards, a step then refuses).  Not run by a session: several ranks (a collective
+    layers and num_edit_tokens are fixed at construction, mom2_update_weight and edit_weight change through ``rescale`` alone
+    (``hparams`` may be mutated by hand afterwards, a step then refuses).  Not run by a session: several ranks (a collective
     ``ConceptShard``), SDXL, cross-attention edits, EMCID_SOLVER=direct|lu; there is no pivoted-LU fallback either — a
     non-positive pivot restores the weights and raises ``torch.linalg.LinAlgError``."""
 
@@ -960,6 +981,8 @@ class EditSession:
         self._folded_sources: set = set()                    # sources whose rows a fold took: no longer releasable
         self._retains = 0                                    # retain() calls so far (the ordinal of a retained row)
         self._release_ws: Optional[hip.ReleaseWorkspace] = None
+        self._rescale_ws: Optional[hip.RescaleWorkspace] = None
+        self._rescales = 0                                   # hip.session_rescale calls so far (LAST_PATHS session_rescales)
         self.released = 0                                    # rows released so far
         self.keep_folded = bool(keep_folded)
         self._archive: Optional[List[torch.Tensor]] = None   # keep_folded: per edited layer (rows, dp) f64, the Q rows every fold added
@@ -1152,9 +1175,24 @@ class EditSession:
                     f"{where}: {what} ({e}); {undone}nothing was added to the {self.preserved} preserved rows") from e
 
     def apply(self, requests: List[Dict], cache_name: Optional[str] = None, return_orig_text_encoder: bool = False, shard=None,
-              stage1=None):
-        """One step: edit ``requests`` with every earlier step's keys preserved.  Returns what apply_emcid_to_text_encoder does."""
+              stage1=None, point=None):
+        """One step: edit ``requests`` with every earlier step's keys preserved.  Returns what apply_emcid_to_text_encoder does.
+        ``point=(mom2_weight, edit_weight)``: ``rescale`` to that pair, then the step, as ONE operation — a step that fails (a
+        non-positive pivot, a stale-cache retry that fails again, any exception) takes the rescale back with it."""
         n = self._check_step(requests, shard)       # raises before anything is launched or allocated
+        if point is not None:
+            (lam_p, e_p), = edit_engine.validate_grid([point])
+            self._refuse_rescale(shard, "apply(point=)")
+            if self.preserved + n > self.capacity:
+                raise ValueError(f"apply(point=): {self.preserved} preserved + {n} new rows would fold the set first, and a session "
+                                 f"that has folded (one that steps on private factors) cannot be rescaled; fold() and keep the "
+                                 f"session's point, or rescale() before the set is full")
+            undo = self._rescale(lam_p, e_p, shard, "apply(point=)")
+            try:
+                return self.apply(requests, cache_name, return_orig_text_encoder, shard, stage1)
+            except BaseException:
+                undo()
+                raise
         if self.preserved + n > self.capacity:      # (on_full="fold": the step fits once the preserved rows are folded)
             self.fold()
         origin_text_encoder = deepcopy(self.pipe.text_encoder) if return_orig_text_encoder else None
@@ -1358,6 +1396,265 @@ class EditSession:
                   f"{self.folded} folded")
         return len(rel)
 
+    # ---- another point, another weight, a sweep of one step -------------------------------------------------------------------
+
+    def _refuse_rescale(self, shard, what: str):
+        """What rescale / reweight / sweep refuse before anything is launched or allocated, on top of ``_check_call``."""
+        self._check_call([None], shard, what)
+        if self.private_factors is not None or self.folded > 0:
+            # (private factors outlive their rows: a keep_folded session that released every folded source still steps on them)
+            raise ValueError(f"{what} on a session that has folded ({self.folded} folded rows, {self.folds} folds): its steps run on "
+                             f"private factors of a C + Pf^T Pf at the point of the fold, a sum no scalar rescales (base += (a' - a) C "
+                             f"and a refactorization is not implemented); restore() starts over")
+
+    def _scale_rows(self, dev_factors: torch.Tensor, first: int, what: str, extra_info: Optional[torch.Tensor] = None):
+        """The device half of rescale / reweight: rows [first, M) of every edited layer scaled in place by ``dev_factors`` (M,) and
+        everything behind ``first`` rebuilt (``hip.session_rescale``), after rows [first, M) of Yp, Lp and the touched tile inverses
+        were copied; ONE pinned flag read (``extra_info``: a second flag word read with it), and on a non-zero flag the copy put
+        back and ``torch.linalg.LinAlgError``.  Returns ``undo()``, which puts the copy back later."""
+        keys, M = self.keys, self.preserved
+        dev = keys.Yp[0].device
+        ws = self._rescale_ws
+        if ws is None or ws.key != (M - first, keys.d, keys.capacity):
+            self._rescale_ws = None                 # (drop the old one first: the largest is of the order of the state itself)
+            ws = self._rescale_ws = hip.RescaleWorkspace(M - first, keys.d, keys.capacity, dev)
+        t0, t1 = first // hip.NB, (M + hip.NB - 1) // hip.NB
+        snap = [(keys.Yp[i][first:M].clone(), keys.Lp[i][first:M].clone(), keys.tile_inv[i][t0:t1].clone())
+                for i in range(keys.n_layers)]
+
+        def undo():
+            for i, (y, l, t) in enumerate(snap):
+                keys.Yp[i][first:M].copy_(y)
+                keys.Lp[i][first:M].copy_(l)
+                keys.tile_inv[i][t0:t1].copy_(t)
+
+        ws.info.zero_()
+        for i in range(keys.n_layers):
+            hip.session_rescale(keys, i, dev_factors, first, ws=ws)
+        self._rescales += keys.n_layers
+        clip_forward.LAST_PATHS["session_rescales"] = self._rescales
+        code = self._read_flag(ws.info if extra_info is None else torch.maximum(ws.info, extra_info.to(ws.info.device)))
+        if code != 0:
+            undo()
+            ws.info.zero_()
+            raise torch.linalg.LinAlgError(
+                f"{what} after step {self.steps}: the system of the {M - first} scaled rows behind row {first} (or lam C' at the new "
+                f"point) is not positive definite (non-positive pivot at column {code - 1}); the {M} preserved rows, the session's "
+                f"point and the weights are as they were")
+        return undo
+
+    def _rescale(self, mom2_weight, edit_weight, shard, what: str):
+        """``rescale`` proper; returns ``undo()``, which makes the session what it was before (``apply(point=)`` calls it when its
+        step fails)."""
+        lam0, e0, layers, k = self._fixed
+        try:
+            lam = lam0 if mom2_weight is None else float(mom2_weight)
+            e = e0 if edit_weight is None else float(edit_weight)
+        except (TypeError, ValueError) as err:
+            raise ValueError(f"mom2_weight and edit_weight must be numbers (got {mom2_weight!r}, {edit_weight!r})") from err
+        if not (np.isfinite(lam) and lam > 0.0):
+            raise ValueError(f"mom2_update_weight must be positive and finite in a session (got {lam}): the dual solver factors lam C'")
+        if not (0.0 < e < 1.0):
+            raise ValueError(f"edit_weight must lie inside (0, 1) in a session (got {e})")
+        self._refuse_rescale(shard, what)
+        if (lam, e) == (lam0, e0):                  # (the point it is at: nothing to scale, nothing to drop)
+            return lambda: None
+        hp, M = self.hparams, self.preserved
+        before = (self._fixed, hp.mom2_update_weight, hp.edit_weight, self._shared, self._report)
+        undo_rows, scale0 = None, None
+        if M > 0:
+            keys = self.keys
+            dev = keys.Yp[0].device
+            old, covs = self._shared
+            # the factors of (lam', e') the later steps, fold() and save / load take the rows as coordinates of: the factor cache's,
+            # or one batched factorization handed to it
+            fac, commit = edit_engine.session_factors(self.pipe.text_encoder, layers, hp.rewrite_module_tmp, lam, e,
+                                                      dict(zip(layers, covs)), dev)
+            rho = math.sqrt((lam0 * (1.0 - e0)) / (lam * (1.0 - e)))
+            undo_rows = self._scale_rows(torch.full((M,), rho, dtype=torch.float64, device=dev), 0, what, fac.info)
+            commit()
+            # report() divides by row_scale = (raw scale) / sqrt(lam_ratio of the factors in use): P keeps its raw scale, the unit moves
+            scale0 = keys.row_scale[:M].clone()
+            keys.rescale_commit(math.sqrt(old.lam_ratio(lam0) / fac.lam_ratio(lam)))
+            self._shared = (fac, covs)
+        self._fixed = (lam, e, layers, k)
+        hp.mom2_update_weight, hp.edit_weight = lam, e
+        self._report = self._report_pending = None
+        clip_forward.LAST_PATHS["session_preserved_rows"] = M
+
+        def undo():
+            if undo_rows is not None:
+                undo_rows()
+                self.keys.row_scale[:M] = scale0
+            self._fixed, hp.mom2_update_weight, hp.edit_weight, self._shared, self._report = before
+
+        return undo
+
+    def rescale(self, mom2_weight=None, edit_weight=None, shard=None):
+        """The session's mom2_update_weight and edit_weight from now on (``None``: as it is).  Held rows keep the raw scale they were
+        committed with — P does not change, only the base term a C, a = 2 lam (1 - e), does — so per edited layer ONE
+        ``hip.session_rescale`` call with the uniform factor sqrt(a / a') and first = 0 makes the rows coordinates of the new
+        point's factor and rebuilds Lp and the tile inverses: no forward, no statistics read by the rows, no weight moved.  Atomic
+        like ``release``: rows [0, M) of every layer are copied first, all layers run, ONE pinned flag read decides; zero commits
+        all layers together with ``hparams`` (the same two fields the constructor read), the factors later steps, ``fold()`` and
+        ``save`` refer to (those of the new point, from the factor cache as a step takes them) and ``row_scale``; non-zero puts
+        everything back and raises ``torch.linalg.LinAlgError``.  A stored ``report()`` readout is dropped.  With no preserved row
+        only the numbers change; the point the session is at already changes nothing.  ``ValueError`` before anything is
+        launched: a bad value (the constructor's rules), a session that has folded, and what ``apply`` refuses."""
+        self._rescale(mom2_weight, edit_weight, shard, "rescale")
+        if self.verbose:
+            print(f"Session rescale: mom2_update_weight {self._fixed[0]:g}, edit_weight {self._fixed[1]:g}, {self.preserved} preserved")
+
+    def reweight(self, sources, weight: float, shard=None) -> int:
+        """Every live row of ``sources`` (``request["source"]`` strings, or request dicts) counts from now on like a key retained now
+        at ``weight``: its rows are multiplied by (that row scale) / (the one they hold) — 1 for every other row — and everything
+        behind the smallest changed row is rebuilt (``hip.session_rescale``), atomically as in ``rescale``.  No weight of the
+        encoder moves.  Returns the rows changed.  Errors are ``release``'s (``KeyError``: a source without a live row;
+        ``ValueError``: a folded source, an empty list, a weight that is not positive and finite, a folded session, what ``apply``
+        refuses), all before anything is launched or allocated."""
+        try:
+            w = float(weight)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"weight must be a positive finite number (got {weight!r})") from e
+        if not (np.isfinite(w) and w > 0.0):
+            raise ValueError(f"weight must be a positive finite number (got {weight!r})")
+        names = [s["source"] if isinstance(s, dict) else s for s in sources]
+        self._refuse_rescale(shard, "a reweight")
+        keep, _, _ = release_plan(self._ledger, self._folded_sources, names)
+        kept = set(keep)
+        rows = [i for i in range(len(self._ledger)) if i not in kept]
+        M = self.preserved
+        assert M == len(self._ledger) and rows
+        lam, e, _, _ = self._fixed
+        target = hip.row_scale_of(e, self._shared[0], lam, w)
+        f = torch.ones(M, dtype=torch.float64)
+        idx = torch.tensor(rows, dtype=torch.long)
+        f[idx] = target / self.keys.row_scale[idx]
+        changed = [i for i in rows if float(f[i]) != 1.0]
+        if changed:
+            self._scale_rows(f.to(self.keys.Yp[0].device), changed[0], "reweight")
+            self.keys.rescale_commit(f)
+        self._report = self._report_pending = None
+        if self.verbose:
+            print(f"Session reweight: {len(rows)} rows of {len(set(names))} sources at weight {w:g}")
+        return len(rows)
+
+    def sweep(self, requests: List[Dict], grid, cache_name: Optional[str] = None, scorer=None, visit=None, shard=None,
+              stage1=None) -> List[Dict]:
+        """Trial steps of ``requests`` at every (mom2_weight, edit_weight) pair of ``grid`` (``edit_engine.validate_grid``), nothing
+        committed: the sweep -> score -> ``select_point`` workflow on ONE step of a session.  The held rows are copied once and the
+        requests prepared once (tokenization, trie, prefix launches, v* rows: ``edit_engine.SweepWalk``'s shared part, with the
+        statistics factored at unit scale at most once per edited layer); per pair the live state is scaled OUT OF THE COPY to the
+        pair (``hip.session_rescale`` with ``src``), the factors are the unit ones rescaled (``hip.cov_factor_rescale``), the
+        step's chain runs as ``apply`` runs it with its rows behind row M (M is not bumped), the flags are read, the entry is
+        filled and the weights are put back.  Returns one dict per pair: ``point``, ``score`` (``scorer.score()`` of an
+        ``EditScorer`` built on the baseline weights; ``None`` without one), ``report`` (``report()``'s dict on a ``report=True``
+        session), ``visit`` (``visit(pair, pipe)``'s result) and ``error`` (``None``, or the message of the non-positive pivot that
+        point met — the walk goes on; ``torch.linalg.LinAlgError`` only if every point failed).  On return, also when ``visit``
+        raises, the state is back from the copy byte for byte and weights, ``preserved``, ledger, ``steps``, the point and
+        ``hparams`` are as before.  A weight rewritten behind the forward's caches (``StaleWeightCacheError``) has the plan made again
+        once, as for a step, and the walk goes on at the point that met it.  One pinned flag read per point.  Refuses what
+        ``rescale`` refuses, an empty grid or request list, and a step that does not fit."""
+        pts = edit_engine.validate_grid(grid)
+        n = self._check_step(requests, shard)
+        self._refuse_rescale(shard, "a sweep")
+        if self.preserved + n > self.capacity:
+            raise PreservedSetFull(f"{self.preserved} preserved + {n} new concept rows exceed the session's capacity {self.capacity}: "
+                                   f"a sweep does not fold")
+        LP = clip_forward.LAST_PATHS
+        LP["session_sweep_points"] = 0
+        LP["sweep_points"] = LP["sweep_cov_factorizations"] = LP["sweep_prefix_runs"] = 0
+        self._ensure_keys()
+        results: List[Dict] = []
+        for attempt in (0, 1):
+            try:
+                self._sweep_points(requests, pts, n, results, cache_name, scorer, visit, shard, stage1)
+                break
+            except clip_forward.StaleWeightCacheError as e:
+                # (as a step: the plan is made again from the live weights, once; the walk goes on at the point that met it)
+                if attempt == 1:
+                    raise
+                _note_stale("EditSession.sweep", e, "point")
+                LP["stale_cache_retries"] = LP.get("stale_cache_retries", 0) + 1
+            except FloatingPointError as e:         # (EMCID_LU_FALLBACK=0 and statistics that are not positive definite)
+                raise torch.linalg.LinAlgError(f"sweep after step {self.steps}: {e}; nothing was run and the session is as it was") from e
+        if all(r["error"] is not None for r in results):
+            raise torch.linalg.LinAlgError(f"sweep after step {self.steps}: every one of the {len(pts)} points met a non-positive pivot "
+                                           f"(the first: {results[0]['error']}); the session is as it was")
+        return results
+
+    def _sweep_points(self, requests, pts, n, results, cache_name, scorer, visit, shard, stage1):
+        """The walk of ``sweep`` over ``pts[len(results):]`` on a freshly prepared plan; a finished point's entry is appended to
+        ``results``.  Whatever ends it, the held state, ``row_scale``, the stored readout and the weights are put back."""
+        hp, te, LP = self.hparams, self.pipe.text_encoder, clip_forward.LAST_PATHS
+        lam0, e0, _, _ = self._fixed
+        keys, M = self.keys, self.preserved
+        dev = keys.Yp[0].device
+        rows, t1 = min(M + n, keys.capacity), (M + n + hip.NB - 1) // hip.NB
+        plan = prepare_text_encoder_edit(te, self.pipe.tokenizer, requests, hp, hp.layers, hp.mom2_update_weight, self.stats_dir,
+                                         cache_name, "", self.verbose, shard, _default_stage1(self.pipe, hp, stage1))
+        plan.session = self
+        snap = [(keys.Yp[i][:rows].clone(), keys.Lp[i][:rows].clone(), keys.tile_inv[i][:t1].clone()) for i in range(keys.n_layers)]
+        scale0, report0 = keys.row_scale[:M].clone(), self._report
+        rws = own_info = None
+        if M > 0:
+            rws = self._rescale_ws
+            if rws is None or rws.key != (M, keys.d, keys.capacity):
+                self._rescale_ws = None             # (drop the old one first: the largest is of the order of the state itself)
+                rws = self._rescale_ws = hip.RescaleWorkspace(M, keys.d, keys.capacity, dev)
+            own_info = rws.info
+        factor = torch.empty(max(M, 1), dtype=torch.float64, device=dev)[:M]
+        walk = edit_engine.SweepWalk(plan)
+        try:
+            with walk:
+                if walk.unit is None:
+                    raise torch.linalg.LinAlgError("sweep: the statistics C themselves are not positive definite; nothing was run")
+                for lam, e in pts[len(results):]:
+                    entry = {"point": (lam, e), "score": None, "report": None, "visit": None, "error": None}
+                    with phase("sweep: points"):
+                        plan.lam, plan.edit_weight, plan.solver = lam, e, walk.pinned
+                        walk.scaled = hip.cov_factor_rescale(walk.unit, 2.0 * lam * (1.0 - e), walk.scaled, lam=lam, edit_weight=e)
+                        plan.sweep_factors = walk.scaled
+                        if M > 0:
+                            # the rescale reports into the flag word of the point's factors (just zeroed), which check_info reads
+                            # with the step's own: ONE pinned read per point
+                            rws.info = walk.scaled.info
+                            factor.fill_(math.sqrt((lam0 * (1.0 - e0)) / (lam * (1.0 - e))))
+                            for i in range(keys.n_layers):
+                                hip.session_rescale(keys, i, factor, 0, src=snap[i][0], ws=rws)
+                            self._rescales += keys.n_layers
+                            # (the point's factors are at its own lam: a preserved row's unit is its raw scale)
+                            keys.row_scale[:M] = scale0 * math.sqrt(self._shared[0].lam_ratio(lam0))
+                        plan.chunk.state = walk.state
+                        self._report_pending = None
+                        try:
+                            edit_engine.run_encoder_edit(plan, keep_factors=False, restore=False)
+                            check_info(plan)            # (puts the weights back itself before it raises)
+                        except FloatingPointError as err:
+                            entry["error"] = str(err)
+                        LP["session_sweep_points"] += 1
+                    if entry["error"] is None:
+                        if scorer is not None:
+                            entry["score"] = scorer.score()
+                        if self.report_on and self._report_pending is not None:
+                            self._report = self._report_pending
+                            entry["report"] = self.report()
+                        if visit is not None:
+                            entry["visit"] = visit((lam, e), self.pipe)
+                        plan.restore_weights()
+                    results.append(entry)
+        finally:
+            edit_engine._release_workspaces(plan)
+            if rws is not None:
+                rws.info = own_info
+            for i, (y, l, t) in enumerate(snap):
+                keys.Yp[i][:rows].copy_(y)
+                keys.Lp[i][:rows].copy_(l)
+                keys.tile_inv[i][:t1].copy_(t)
+            keys.row_scale[:M] = scale0
+            self._report, self._report_pending = report0, None
+            LP["session_rescales"] = self._rescales
+
     def reset(self):
         """Forget the preserved keys; the weights stay as they are, the next step starts a fresh set (M = 0)."""
         if self.keys is not None:
@@ -1366,11 +1663,12 @@ class EditSession:
         self.private_factors = self._base = self._shared = None
         self.folded = self.folds = self.retained = self.released = self._retains = 0
         self._report = self._report_pending = None
-        self._ledger, self._folded_sources, self._release_ws = [], set(), None
+        self._ledger, self._folded_sources, self._release_ws, self._rescale_ws = [], set(), None, None
         self._archive, self._archived, self._archive_ledger = None, 0, []
         LP = clip_forward.LAST_PATHS
         LP["session_steps"] = LP["session_preserved_rows"] = LP["session_folds"] = LP["session_folded_rows"] = 0
         LP["session_retained_rows"] = LP["session_released_rows"] = 0
+        LP["session_rescales"] = LP["session_sweep_points"] = self._rescales = 0
 
     def restore(self):
         """The edited weights back at their values of before the session's first step (bit-identical), and the keys forgotten."""

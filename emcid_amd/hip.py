@@ -30,7 +30,7 @@ EXPORTS = [
     "emcid_edit_dual_apply_assemble_f64",
     "emcid_edit_dual_preserve_workspace_bytes", "emcid_edit_layer_dual_preserve_f64",
     "emcid_session_retain_workspace_bytes", "emcid_session_retain_f64", "emcid_session_step_norms_f64",
-    "emcid_session_release_workspace_bytes", "emcid_session_release_f64",
+    "emcid_session_release_workspace_bytes", "emcid_session_release_f64", "emcid_session_rescale_f64",
     "emcid_cov_factor_fold_workspace_bytes", "emcid_cov_factor_fold_f64",
     "emcid_session_refold_update_f64", "emcid_cov_factor_refactor_f64",
     "emcid_score_rows_f32", "emcid_score_chains_f64", "emcid_score_chains_pair_f64", "emcid_score_pooled_f32",
@@ -110,6 +110,7 @@ def load():
         "emcid_session_step_norms_f64": (i32, [p, i64, i64, i64, i64, i64, i64, p, p, p, p]),
         "emcid_session_release_workspace_bytes": (i64, [i64, i64, i64]),
         "emcid_session_release_f64": (i32, [p, i64, i64, i64, p, i64, p, i64, p, i64, i64, p, i64, p, p]),
+        "emcid_session_rescale_f64": (i32, [p, p, i64, i64, i64, p, i64, p, i64, p, i64, i64, p, i64, p, p]),
         "emcid_cov_factor_fold_workspace_bytes": (i64, [i64, i64]),
         "emcid_cov_factor_fold_f64": (i32, [p, f64, p, i64, i64, i64, p, f64, f64, i32, p, i64, i64, i64, p, p, i64, p, p]),
         "emcid_session_refold_update_f64": (i32, [p, i64, i64, i64, p, i64, i64, i64, p, i64, i64, p, i64, p, p]),
@@ -1390,6 +1391,14 @@ class PreservedKeys:
         self.row_scale[:len(keep)] = self.row_scale[torch.as_tensor(keep, dtype=torch.long)]
         self.M = len(keep)
 
+    def rescale_commit(self, factors):
+        """Make the committed rows count as scaled by ``factors`` (one positive finite number, or one per committed row), after
+        ``session_rescale`` has run on every layer and the flag word read zero: multiplies the host ``row_scale`` vector.  The
+        factors are those of the UNITS a later ``session_step_norms`` reports in; they are the device factors whenever the
+        coordinates' factor workspace stays what it was (``check_factors`` refuses the rest)."""
+        f = check_factors(factors, self.M)
+        self.row_scale[:self.M] *= f
+
     def reset(self):
         self.M = 0
 
@@ -1598,6 +1607,84 @@ def session_release(state: PreservedKeys, layer_index: int, keep, first: Optiona
     _check(load().emcid_session_release_f64(
         _ptr(keep_dev, torch.int32, "keep"), n_keep, first, state.d, *state.layer_args(layer_index),
         _ptr(ws.buf), ws.nbytes, _ptr(ws.info, torch.int32), _stream(Yp)), "emcid_session_release_f64")
+    return {"ws": ws, "launched": True, "first": first}
+
+
+def check_factors(factors, M: int) -> torch.Tensor:
+    """``factors`` as an (M,) f64 host tensor: one number for every row, or M of them; ``EmcidHipError`` for another length and for
+    a factor that is not positive and finite.  Pure host code."""
+    try:
+        f = torch.as_tensor(factors, dtype=torch.float64, device="cpu").detach()
+    except (TypeError, ValueError, RuntimeError) as e:
+        raise EmcidHipError(f"row factors must be numbers: {e}") from e
+    if f.dim() == 0:
+        f = f.repeat(M)
+    if f.dim() != 1 or f.numel() != M:
+        raise EmcidHipError(f"{tuple(f.shape)} row factors for {M} committed rows")
+    if not bool((torch.isfinite(f) & (f > 0.0)).all()):
+        raise EmcidHipError("row factors must be positive and finite")
+    return f.contiguous()
+
+
+class RescaleWorkspace(_SessionWorkspace):
+    """The workspace of emcid_session_rescale_f64 for a rescale that rebuilds ``n_rebuilt`` rows: the retain workspace of that N
+    (which may equal the capacity)."""
+
+    def __init__(self, n_rebuilt: int, d: int, capacity: int, device):
+        super().__init__("rescale", load().emcid_session_retain_workspace_bytes, dict(n_rebuilt=n_rebuilt, d=d, capacity=capacity),
+                         device)
+
+
+def session_rescale(state: PreservedKeys, layer_index: int, factors, first: Optional[int] = None, src: Optional[torch.Tensor] = None,
+                    ws: Optional[RescaleWorkspace] = None):
+    """Scale the committed rows of layer ``layer_index`` of ``state`` by ``factors`` (one number, or one per committed row; all
+    positive and finite) and rebuild what lies behind ``first``, the smallest row whose factor is not 1 (worked out when None; a
+    smaller one may be given): rows [first, M) of ``src`` (default: the layer's own Yp; else an f64 tensor of >= M rows of the
+    same width on the same device, a copy of them) times their factors become the layer's rows, Lp and the tile inverses behind
+    ``first`` follow as the key half of a step (include/emcid_hip.h, emcid_session_rescale_f64).  Nothing is committed here
+    (``state.rescale_commit(...)`` after the flag word ``ws.info`` read zero, for all layers together).  All factors 1 with no
+    ``src``, and M = 0, launch nothing.  ``factors`` may be an (M,) f64 tensor on the state's device (then ``first`` must be
+    given and nothing is checked on the host).  Returns dict(ws | None, launched, first)."""
+    state.check_layer(layer_index)
+    Yp, M = state.Yp[layer_index], state.M
+    if isinstance(factors, torch.Tensor) and factors.is_cuda:
+        if first is None:
+            raise EmcidHipError("session_rescale: a device tensor of factors needs `first`")
+        if factors.dtype != torch.float64 or not factors.is_contiguous() or factors.numel() != M or factors.device != Yp.device:
+            raise EmcidHipError(f"session_rescale: factors must be a contiguous f64 tensor of {M} elements on {Yp.device}")
+        f_dev, first = factors, int(first)
+    else:
+        f = check_factors(factors, M)
+        changed = torch.nonzero(f != 1.0).flatten()
+        lowest = int(changed[0]) if changed.numel() else M
+        if first is None:
+            first = 0 if src is not None else lowest
+        first = int(first)
+        if not 0 <= first <= M:
+            raise EmcidHipError(f"session_rescale: first = {first}, {M} committed")
+        if first > lowest:
+            raise EmcidHipError(f"session_rescale: first = {first}, but row {lowest} has the factor {float(f[lowest])}")
+        f_dev = None
+    if not 0 <= first <= M:
+        raise EmcidHipError(f"session_rescale: first = {first}, {M} committed")
+    if first == M:
+        return {"ws": None, "launched": False, "first": first}
+    if not Yp.is_cuda:
+        raise EmcidHipError(f"session_rescale runs on a state in HBM (got {Yp.device}); there is no CPU path")
+    if src is not None:
+        if not isinstance(src, torch.Tensor) or src.dtype != torch.float64 or src.dim() != 2 or src.device != Yp.device or \
+                src.shape[0] < M or src.shape[1] < state.dp or src.stride(1) != 1 or src.stride(0) % 2 or src.data_ptr() % 16:
+            raise EmcidHipError(f"session_rescale: src must be an f64 tensor of >= ({M}, {state.dp}) on {Yp.device}, rows contiguous")
+    if f_dev is None:
+        f_dev = f.to(Yp.device)
+    n_rebuilt = M - first
+    if ws is None or ws.key != (n_rebuilt, state.d, state.capacity):
+        ws = RescaleWorkspace(n_rebuilt, state.d, state.capacity, Yp.device)
+    s = Yp if src is None else src
+    _check(load().emcid_session_rescale_f64(
+        _ptr(f_dev, torch.float64, "factors"), _ptr(s, torch.float64, "src"), s.stride(0), first, state.d,
+        *state.layer_args(layer_index), _ptr(ws.buf), ws.nbytes, _ptr(ws.info, torch.int32), _stream(Yp)),
+        "emcid_session_rescale_f64")
     return {"ws": ws, "launched": True, "first": first}
 
 

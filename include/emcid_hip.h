@@ -462,6 +462,24 @@ int emcid_session_release_f64(const int32_t* keep_dev, int64_t n_keep, int64_t f
                               int64_t ldl, double* tile_inv, int64_t capacity, int64_t M, void* workspace, int64_t workspace_bytes,
                               int* info_dev, void* stream);
 
+/* RESCALE rows of a preserved key set (edit sessions: another mom2_update_weight / edit_weight from now on, or another weight for
+ * some held concepts; entry point added under ABI 16).  Row i of Yp becomes factors_dev[i] * row i of src_Yp [>= M rows][lds] for
+ * first <= i < M, and everything behind `first` is rebuilt: the scaled rows go through the workspace (src_Yp may be Yp itself: source
+ * and destination then overlap) and re-enter as the key half of the step above with M = first, N = M - first,
+ *     B = Yk Yp^T,  Lkp = B Lp^-T,  T = I + Yk Yk^T - Lkp Lkp^T = Lkk Lkk^T,  append [Lkp Lkk],  extend the tile inverses
+ * — the launches of a release plus one scaling pass (one fp64 multiply per element); no forward, no X, no statistics, no weights.
+ * With a = 2 lam (1 - e) the base term of a session is a C and chol(a' C) = sqrt(a' / a) chol(a C): a new (lam', e') is the
+ * uniform factor sqrt(a / a') with first = 0; a new weight w' of a row held at w is sqrt(w' / w) for that row, 1 elsewhere, first =
+ * the smallest changed row.  factors_dev [M] f64 in HBM, positive and finite (the caller's word; entries below `first` are not
+ * read).  ONE layer per call, no host synchronisation.  Rows < first of Yp and Lp and the tiles wholly below `first` are never
+ * written (with src_Yp != Yp rows < first of Yp must already equal those of src_Yp); rows >= M are left as they are; info_dev
+ * reports a non-positive pivot of T as the retain entry does, and the caller then puts its copy of rows [first, M) back.  Needs
+ * 0 <= first < M <= capacity: all factors 1 (first == M) is no call.  workspace: emcid_session_retain_workspace_bytes(M - first, d,
+ * capacity) — N = M - first may equal the capacity (first = 0: B is not touched). */
+int emcid_session_rescale_f64(const double* factors_dev, const double* src_Yp, int64_t lds, int64_t first, int64_t d, double* Yp,
+                              int64_t ldy, double* Lp, int64_t ldl, double* tile_inv, int64_t capacity, int64_t M, void* workspace,
+                              int64_t workspace_bytes, int* info_dev, void* stream);
+
 /* The readout of a preserve step, from what it left in its workspace.  With Z = (I + Y Y^T)^-1 [0; Rt] (Y = [Yp; Yk]) the step
  * moves every preserved key by dW p_i = -Zp_i and leaves Zk_j of each new residual; ZT = [Zp^T | Zk^T] and Rt are still in the
  * workspace when the step returns.  Called stream-ordered right after emcid_edit_layer_dual_preserve_f64 on the SAME workspace
