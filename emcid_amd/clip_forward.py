@@ -42,8 +42,9 @@ SPLIT_GEMM = os.environ.get("EMCID_SPLIT_GEMM", "1") != "0"
 # exact-f32 kernel / torch's F.linear; layers issued by the native runner; forwards that took the trie / the hooked HF encoder;
 # trie forwards that had to FALL BACK to the hooked HF encoder (each one is also logged once per reason).  sweep_*: gauges of the
 # last sweep_emcid_text_encoder (edit_engine.run_sweep): its points, the covariance factorizations it ran, its prefix runs.
-# session_*: gauges of the last EditSession step (emcid_main.EditSession): its steps so far and preserved concept rows; its folds
-# and the rows they took into the session's base factor; the rows its retain lists added (EditSession.retain), folded ones included.
+# session_*: gauges of the last EditSession operation (edit_session.EditSession, written by its _publish alone from the table
+# edit_session._GAUGES): its steps so far and preserved concept rows; its folds and the rows they took into the session's base
+# factor; the rows its retain lists added (EditSession.retain), folded ones included; session_loaded_rows appears with a load.
 # session_rescales: hip.session_rescale calls of the session so far (rescale, reweight, the points of a sweep; one per edited layer);
 # session_sweep_points: the points the last EditSession.sweep ran.
 # score_replays: replays of the trie forward made by an emcid_main.EditScorer (its construction and every score()).

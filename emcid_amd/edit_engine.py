@@ -142,7 +142,7 @@ class EncoderEditPlan:
     factors_from_cache: bool = False
     num_edit_tokens: int = 1             # k > 1: k key / value rows per request (last subject token, EOS, padding), n_total = N k
     sweep_factors: Optional[hip.CovFactors] = None       # set by run_sweep: the point's rescaled factors, used as they are
-    session: object = None               # set by emcid_main.EditSession: the preserved keys (``.keys``: hip.PreservedKeys) of the earlier steps
+    session: object = None               # set by edit_session.EditSession: the preserved keys (``.keys``: hip.PreservedKeys) of the earlier steps
     retain_weight: Optional[float] = None    # set by EditSession.retain: the pass only ENTERS its keys into the session's set (no targets, no weight written)
 
     def weight_name(self, layer):
@@ -582,7 +582,7 @@ def _dual_factors(plan: EncoderEditPlan, form: str, dev):
         return None, False
     private = plan.session.private_factors if plan.session is not None else None
     if private is not None:
-        # a session that has folded its preserved keys: the factors of lam C' + P^T P, the session's own (emcid_main.EditSession.fold)
+        # a session that has folded its preserved keys: the factors of lam C' + P^T P, the session's own (edit_session.EditSession.fold)
         plan.cov_factors, plan.factors_from_cache = private, True
         return None, False
     fkey = factor_cache_key([plan.covs[l] for l in plan.layers], plan.lam, plan.edit_weight)
@@ -648,7 +648,7 @@ def _cache_own_factors(plan: EncoderEditPlan):
 def session_factors(text_encoder, layers, rewrite_module_tmp: str, lam: float, edit_weight: float, covs: Dict[int, torch.Tensor], dev):
     """The factors of lam C' of every edited layer with their explicit inverses, obtained the way a session step obtains them
     (``_dual_factors``: the factor cache under the key plain calls use, else one batched factorization on the side stream) but
-    without a pass — what ``emcid_main.EditSession.load`` takes as the coordinates of the rows it loads.  The current stream waits
+    without a pass — what ``edit_session.EditSession.load`` takes as the coordinates of the rows it loads.  The current stream waits
     for them.  Returns (factors, commit): ``commit()``, to be called once the caller has read ``factors.info`` as zero, hands
     factors made here to the cache as ``check_info`` does (nothing to do after a cache hit)."""
     plan = EncoderEditPlan(text_encoder, list(layers), rewrite_module_tmp, float(lam), float(edit_weight), None, None, covs, 0)

@@ -213,6 +213,13 @@ def _stream(t: torch.Tensor):
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
+def pinned_copy(t: torch.Tensor) -> torch.Tensor:
+    """``t`` on its way to page-locked host memory: the copy is queued on the current stream, not waited for."""
+    out = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+    out.copy_(t.detach(), non_blocking=True)
+    return out
+
+
 # ---- Stage 0 -----------------------------------------------------------------------------------------
 
 GRAM_SPLIT = os.environ.get("EMCID_GRAM_SPLIT", "1") != "0"      # 0: always the exact-f32 MFMA SYRK
@@ -1402,6 +1409,9 @@ class PreservedKeys:
     def reset(self):
         self.M = 0
 
+    def snapshot(self, first: int, end: int) -> "KeySnapshot":
+        return KeySnapshot(self, first, end)
+
     def state_dict(self, sync: bool = True) -> dict:
         """The committed part, on the host, in a form that knows nothing of ``capacity`` (so of ``ldl`` and the tile count): per
         layer ``Yp`` (M, d) — the padding columns are zero by construction —, ``Lp`` (M, M) and ``tile_inv`` (ceil(M / 128), 128,
@@ -1414,11 +1424,7 @@ class PreservedKeys:
         w = M - NB * (tiles - 1)                    # rows of the last tile that count
 
         def host(t: torch.Tensor) -> torch.Tensor:
-            if not t.is_cuda:
-                return t.clone()
-            out = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
-            out.copy_(t, non_blocking=True)
-            return out
+            return pinned_copy(t) if t.is_cuda else t.clone()
 
         def tile_part(ti: torch.Tensor) -> torch.Tensor:
             ti = ti[:tiles].clone()
@@ -1470,9 +1476,34 @@ class PreservedKeys:
         return sum(t.numel() * 8 for ts in (self.Yp, self.Lp, self.tile_inv) for t in ts)
 
 
+class KeySnapshot:
+    """Copies of rows [first, end) of every layer's Yp and Lp of a ``PreservedKeys``, of the tile inverses those rows touch (tiles
+    [first // NB, ceil(end / NB))) and of the host ``row_scale`` of the committed rows; ``restore()`` copies all of it back to
+    where it came from.  ``Yp[i]`` is layer i's copy, a contiguous (end - first, dp) tensor.  first == end holds nothing."""
+
+    def __init__(self, state: PreservedKeys, first: int, end: int):
+        self.state, self.rows = state, slice(first, end)
+        self.tiles = slice(first // NB, (end + NB - 1) // NB if end > first else first // NB)
+        self.Yp = [t[self.rows].clone() for t in state.Yp]
+        self.Lp = [t[self.rows].clone() for t in state.Lp]
+        self.tile_inv = [t[self.tiles].clone() for t in state.tile_inv]
+        self.row_scale = state.row_scale[:state.M if end > first else 0].clone()
+
+    def restore(self):
+        s = self.state
+        for kept, live, part in ((self.Yp, s.Yp, self.rows), (self.Lp, s.Lp, self.rows), (self.tile_inv, s.tile_inv, self.tiles)):
+            for k, t in zip(kept, live):
+                t[part].copy_(k)
+        s.row_scale[:self.row_scale.numel()] = self.row_scale
+
+
 class _SessionWorkspace:
     """HBM workspace (+ the device `info` word) of one session entry of the library: ``size_fn(*dims.values())`` bytes, ``key``
-    the dimensions it was sized for."""
+    the dimensions it was sized for; ``fitting``: ``ws`` if it was sized for ``dims``, else a new one of this class for them."""
+
+    @classmethod
+    def fitting(cls, ws, device, *dims):
+        return ws if ws is not None and ws.key == dims else cls(*dims, device)
 
     def __init__(self, what: str, size_fn, dims: dict, device):
         self.key = tuple(dims.values())
@@ -1522,8 +1553,7 @@ def edit_layer_dual_preserve(K, Zc, zs_t, factors: CovFactors, layer_index: int,
         raise EmcidHipError("edit_layer_dual_preserve needs the explicit inverse factor of the layer (cov_inverse)")
     if state.M + N > state.capacity:
         raise EmcidHipError(f"{state.M} preserved + {N} new rows exceed the state's capacity {state.capacity}")
-    if ws is None or ws.key != (N, d, h, state.capacity):
-        ws = PreserveWorkspace(N, d, h, state.capacity, K.device)
+    ws = PreserveWorkspace.fitting(ws, K.device, N, d, h, state.capacity)
     dW = torch.empty(h, d, dtype=torch.float32, device=K.device) if want_dw else None
     U = torch.empty(h, d, dtype=torch.float64, device=K.device) if want_u else None
     _check(load().emcid_edit_layer_dual_preserve_f64(
@@ -1557,8 +1587,7 @@ def session_retain(K, factors: CovFactors, layer_index: int, row_scale: float, s
     row_scale = float(row_scale)
     if not (row_scale > 0.0 and row_scale < float("inf")):
         raise EmcidHipError(f"row_scale must be positive and finite (got {row_scale})")
-    if ws is None or ws.key != (N, d, state.capacity):
-        ws = RetainWorkspace(N, d, state.capacity, K.device)
+    ws = RetainWorkspace.fitting(ws, K.device, N, d, state.capacity)
     _check(load().emcid_session_retain_f64(
         _ptr(K, torch.float32, "K"), N, d, row_scale, factors.lam_ratio(lam), _ptr(factors.buf), factors.n_layers, int(layer_index),
         *state.layer_args(layer_index), _ptr(ws.buf), ws.nbytes, _ptr(ws.info, torch.int32), _stream(K)), "emcid_session_retain_f64")
@@ -1601,9 +1630,7 @@ def session_release(state: PreservedKeys, layer_index: int, keep, first: Optiona
         return {"ws": None, "launched": False, "first": first}
     if keep_dev is None:
         keep_dev = torch.tensor(rows, dtype=torch.int32, device=Yp.device)
-    n_rebuilt = n_keep - first
-    if ws is None or ws.key != (n_rebuilt, state.d, state.capacity):
-        ws = ReleaseWorkspace(n_rebuilt, state.d, state.capacity, Yp.device)
+    ws = ReleaseWorkspace.fitting(ws, Yp.device, n_keep - first, state.d, state.capacity)
     _check(load().emcid_session_release_f64(
         _ptr(keep_dev, torch.int32, "keep"), n_keep, first, state.d, *state.layer_args(layer_index),
         _ptr(ws.buf), ws.nbytes, _ptr(ws.info, torch.int32), _stream(Yp)), "emcid_session_release_f64")
@@ -1677,9 +1704,7 @@ def session_rescale(state: PreservedKeys, layer_index: int, factors, first: Opti
             raise EmcidHipError(f"session_rescale: src must be an f64 tensor of >= ({M}, {state.dp}) on {Yp.device}, rows contiguous")
     if f_dev is None:
         f_dev = f.to(Yp.device)
-    n_rebuilt = M - first
-    if ws is None or ws.key != (n_rebuilt, state.d, state.capacity):
-        ws = RescaleWorkspace(n_rebuilt, state.d, state.capacity, Yp.device)
+    ws = RescaleWorkspace.fitting(ws, Yp.device, M - first, state.d, state.capacity)
     s = Yp if src is None else src
     _check(load().emcid_session_rescale_f64(
         _ptr(f_dev, torch.float64, "factors"), _ptr(s, torch.float64, "src"), s.stride(0), first, state.d,
