@@ -1,9 +1,9 @@
-// The readout of an edit score (emcid_main.EditScorer): what an edit did to the text encoder's own output, reduced on the device.
+// The readout of an edit score (edit_score.EditScorer): what an edit did to the text encoder's own output, reduced on the device.
 //   score_rows_kernel    per row pair (a, b) [and a target t]: the sums a relative distance, a cosine and a residual ratio are made
 //                        of, optionally behind a LayerNorm of both rows — fp64 from exact conversions of the fp32 inputs
 //   score_chains_kernel  per prompt: max / mean / end value of a per-node ratio over the prompt's chain of trie nodes
 // Both follow add_layernorm_wave_kernel (attention.hip): one wave per row or prompt, four per workgroup, reductions by shuffles,
-// no LDS, no atomics, plain vector loads and stores.  For the SDXL pair of encoders (emcid_main.PairEditScorer):
+// no LDS, no atomics, plain vector loads and stores.  For the SDXL pair of encoders (edit_score.PairEditScorer):
 //   score_chains_pair_kernel  score_chains_kernel over the concatenated columns of two encoders, each with a trie of its own
 //   score_chains_pair_grid_kernel  score_chains_pair_kernel for every combination of a bank of node sums per encoder (a sweep)
 //   score_pooled_kernel       per row pair: the sums the relative distance of text_projection(final_layer_norm(.)) is made of;
@@ -166,67 +166,110 @@ __global__ __launch_bounds__(256) void score_rows_kernel(const float* __restrict
     }
 }
 
+// ---- one prompt's chain, reduced by one wave: the pieces the three chain kernels below are made of --------------------------------
+// A lane takes the chain positions lane and lane + 64.  Every index is checked before the load it is used in.
+
+__device__ __forceinline__ bool in_range(int64_t i, int64_t n) { return i >= 0 && i < n; }
+
+// The admission of one chain: its length depth[e] + 1 if 1 <= n <= 128 and n <= ld_anc, else 0.  ``e_ok``: e is a node of the
+// trie (depth[e] is not read otherwise).
+__device__ __forceinline__ int chain_admit(bool e_ok, int64_t e, const int32_t* __restrict__ depth, int64_t ld_anc) {
+    const int n = e_ok ? depth[e] + 1 : 0;
+    return (n >= 1 && n <= 128 && n <= ld_anc) ? n : 0;
+}
+
+// The lane's two entries u[j] of the admitted chain anc[e][0 .. n) (n = 0: nothing is read); false when one lies outside [0, U).
+__device__ __forceinline__ bool chain_entries(const int32_t* __restrict__ anc, int64_t e, int64_t ld_anc, int64_t U, int n, int lane,
+                                              int64_t (&u)[2]) {
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        u[j] = 0;
+        if (lane + 64 * j < n) {
+            u[j] = anc[e * ld_anc + lane + 64 * j];
+            ok = ok && in_range(u[j], U);
+        }
+    }
+    return ok;
+}
+
+__device__ __forceinline__ double chain_ratio(double num, double den) { return (num == 0.0 && den == 0.0) ? 0.0 : sqrt(num / den); }
+
+struct ChainAcc {
+    double best, sum, last;
+    int best_pos;
+};
+
+// The lane's share of a chain of n nodes: sums(j) = (num, den) of position lane + 64 j, asked for where take[j].
+template <class Sums>
+__device__ __forceinline__ ChainAcc chain_lane(const bool (&take)[2], int lane, int n, Sums sums) {
+    ChainAcc a = {-1.0, 0.0, 0.0, 1 << 30};
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int pos = lane + 64 * j;
+        if (take[j]) {
+            const double2 s = sums(j);
+            const double r = chain_ratio(s.x, s.y);
+            a.sum += r;
+            if (r > a.best) {         // (positions ascend within a lane: an equal later value does not replace)
+                a.best = r;
+                a.best_pos = pos;
+            }
+            if (pos == n - 1) a.last = r;
+        }
+    }
+    return a;
+}
+
+// The 64 lanes' shares into every lane: the sum, the end value (one lane holds it, the others 0), the max at its first position.
+__device__ __forceinline__ void chain_wave(ChainAcc& a) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a.sum += __shfl_xor(a.sum, o, 64);
+        a.last += __shfl_xor(a.last, o, 64);
+        const double ob = __shfl_xor(a.best, o, 64);
+        const int op = __shfl_xor(a.best_pos, o, 64);
+        if (ob > a.best || (ob == a.best && op < a.best_pos)) {
+            a.best = ob;
+            a.best_pos = op;
+        }
+    }
+}
+
+// Lane 0 writes out4[0..3] = {max, mean, end value, position of the max}, or four NaN for a refused prompt.
+__device__ __forceinline__ void chain_write(double* __restrict__ out4, int lane, bool bad, const ChainAcc& a, int n) {
+    if (lane != 0) return;
+    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    double2* o = reinterpret_cast<double2*>(out4);
+    o[0] = bad ? make_double2(nan, nan) : make_double2(a.best, a.sum / (double)n);
+    o[1] = bad ? make_double2(nan, nan) : make_double2(a.last, (double)a.best_pos);
+}
+
 // out[p][0..3] = {max, mean, value at the end node, chain position of the max (the first one on a tie)} of
 // r(u) = sqrt(node[u][0] / node[u][1]) (0 when both sums are 0) over the chain anc[e][0 .. depth[e]] of e = end_node[p].
-// A lane takes positions lane and lane + 64.  An end node outside [0, U), a chain longer than 128 or than ld_anc, or a chain
-// entry outside [0, U) reads nothing: the prompt's four outputs are NaN.
+// An end node outside [0, U), a chain longer than 128 or than ld_anc, or a chain entry outside [0, U) reads nothing more: the
+// prompt's four outputs are NaN.
 __global__ __launch_bounds__(256) void score_chains_kernel(const double* __restrict__ node, int64_t U, const int32_t* __restrict__ anc,
                                                             int64_t ld_anc, const int32_t* __restrict__ depth,
                                                             const int64_t* __restrict__ end_node, int B, double* __restrict__ out) {
     const int lane = threadIdx.x & 63;
     const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (p >= B) return;
+    if (p >= B) return;       // (whole waves leave)
     const int64_t e = end_node[p];
-    const bool e_ok = e >= 0 && e < U;
-    const int n = e_ok ? depth[e] + 1 : 0;
-    bool ok = e_ok && n >= 1 && n <= 128 && n <= ld_anc;
-    double best = -1.0, sum = 0.0, last = 0.0;
-    int best_pos = 1 << 30;
-    if (ok) {
-        const int32_t* chain = anc + e * ld_anc;
+    const int n = chain_admit(in_range(e, U), e, depth, ld_anc);
+    int64_t u[2];
+    const bool ok = chain_entries(anc, e, ld_anc, U, n, lane, u) && n >= 1;
+    bool take[2];
+    double2 v[2];
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int pos = lane + 64 * j;
-            if (pos < n) {
-                const int64_t u = chain[pos];
-                if (u < 0 || u >= U) {
-                    ok = false;
-                } else {
-                    const double2 v = *reinterpret_cast<const double2*>(node + u * 8);
-                    const double r = (v.x == 0.0 && v.y == 0.0) ? 0.0 : sqrt(v.x / v.y);
-                    sum += r;
-                    if (r > best) {         // (positions ascend within a lane: an equal later value does not replace)
-                        best = r;
-                        best_pos = pos;
-                    }
-                    if (pos == n - 1) last = r;
-                }
-            }
-        }
+    for (int j = 0; j < 2; ++j) {
+        take[j] = ok && lane + 64 * j < n;
+        if (take[j]) v[j] = *reinterpret_cast<const double2*>(node + u[j] * 8);
     }
+    ChainAcc a = chain_lane(take, lane, n, [&](int j) { return v[j]; });
     const int bad = __any(!ok);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        sum += __shfl_xor(sum, o, 64);
-        last += __shfl_xor(last, o, 64);       // (one lane holds the end value, the others 0)
-        const double ob = __shfl_xor(best, o, 64);
-        const int op = __shfl_xor(best_pos, o, 64);
-        if (ob > best || (ob == best && op < best_pos)) {
-            best = ob;
-            best_pos = op;
-        }
-    }
-    if (lane == 0) {
-        double2* o = reinterpret_cast<double2*>(out + (int64_t)p * 4);
-        if (bad) {
-            const double nan = __longlong_as_double(0x7ff8000000000000LL);
-            o[0] = make_double2(nan, nan);
-            o[1] = make_double2(nan, nan);
-        } else {
-            o[0] = make_double2(best, sum / (double)n);
-            o[1] = make_double2(last, (double)best_pos);
-        }
-    }
+    chain_wave(a);
+    chain_write(out + (int64_t)p * 4, lane, bad, a, n);
 }
 
 // score_chains_kernel over the columns of TWO encoders (an SDXL UNet is conditioned on the concatenation of their token states):
@@ -243,59 +286,26 @@ __global__ __launch_bounds__(256) void score_chains_pair_kernel(const double* __
     const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (p >= B) return;
     const int64_t e1 = end1[p], e2 = end2[p];
-    const bool e_ok = e1 >= 0 && e1 < U1 && e2 >= 0 && e2 < U2;
-    const int n = e_ok ? depth1[e1] + 1 : 0, n2 = e_ok ? depth2[e2] + 1 : 0;
-    bool ok = e_ok && n == n2 && n >= 1 && n <= 128 && n <= ld_anc1 && n <= ld_anc2;
-    double best = -1.0, sum = 0.0, last = 0.0;
-    int best_pos = 1 << 30;
-    if (ok) {
-        const int32_t* c1 = anc1 + e1 * ld_anc1;
-        const int32_t* c2 = anc2 + e2 * ld_anc2;
+    const bool e_ok = in_range(e1, U1) && in_range(e2, U2);
+    const int na = chain_admit(e_ok, e1, depth1, ld_anc1), nb = chain_admit(e_ok, e2, depth2, ld_anc2);
+    const int n = na == nb ? na : 0;
+    int64_t u1[2], u2[2];
+    const bool ok1 = chain_entries(anc1, e1, ld_anc1, U1, n, lane, u1), ok2 = chain_entries(anc2, e2, ld_anc2, U2, n, lane, u2);
+    const bool ok = ok1 && ok2 && n >= 1;
+    bool take[2];
+    double2 v1[2], v2[2];
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int pos = lane + 64 * j;
-            if (pos < n) {
-                const int64_t u1 = c1[pos], u2 = c2[pos];
-                if (u1 < 0 || u1 >= U1 || u2 < 0 || u2 >= U2) {
-                    ok = false;
-                } else {
-                    const double2 v1 = *reinterpret_cast<const double2*>(node1 + u1 * 8);
-                    const double2 v2 = *reinterpret_cast<const double2*>(node2 + u2 * 8);
-                    const double num = v1.x + v2.x, den = v1.y + v2.y;
-                    const double r = (num == 0.0 && den == 0.0) ? 0.0 : sqrt(num / den);
-                    sum += r;
-                    if (r > best) {
-                        best = r;
-                        best_pos = pos;
-                    }
-                    if (pos == n - 1) last = r;
-                }
-            }
+    for (int j = 0; j < 2; ++j) {
+        take[j] = ok && lane + 64 * j < n;
+        if (take[j]) {
+            v1[j] = *reinterpret_cast<const double2*>(node1 + u1[j] * 8);
+            v2[j] = *reinterpret_cast<const double2*>(node2 + u2[j] * 8);
         }
     }
+    ChainAcc a = chain_lane(take, lane, n, [&](int j) { return make_double2(v1[j].x + v2[j].x, v1[j].y + v2[j].y); });
     const int bad = __any(!ok);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        sum += __shfl_xor(sum, o, 64);
-        last += __shfl_xor(last, o, 64);
-        const double ob = __shfl_xor(best, o, 64);
-        const int op = __shfl_xor(best_pos, o, 64);
-        if (ob > best || (ob == best && op < best_pos)) {
-            best = ob;
-            best_pos = op;
-        }
-    }
-    if (lane == 0) {
-        double2* o = reinterpret_cast<double2*>(out + (int64_t)p * 4);
-        if (bad) {
-            const double nan = __longlong_as_double(0x7ff8000000000000LL);
-            o[0] = make_double2(nan, nan);
-            o[1] = make_double2(nan, nan);
-        } else {
-            o[0] = make_double2(best, sum / (double)n);
-            o[1] = make_double2(last, (double)best_pos);
-        }
-    }
+    chain_wave(a);
+    chain_write(out + (int64_t)p * 4, lane, bad, a, n);
 }
 
 constexpr int GRID_CHUNK = 16;       // combinations per blockIdx.y of score_chains_pair_grid_kernel
@@ -303,12 +313,12 @@ constexpr int GRID_FLIGHT = 4;       // of them, those whose node sums are all l
 
 // score_chains_pair_kernel for every combination c < C of a point of encoder 1 with a point of encoder 2 (a sweep over the pair,
 // emcid_main.sweep_emcid_sdxl_text_encoders): node_e is a BANK [G_e][U_e][8] of score_rows outputs, combo [C][2] names a bank
-// entry of each, and out[c][p][0..3] is what score_chains_pair_kernel writes for prompt p on those two entries — the same
-// operations in the same order, the same shuffle tree, the same tie rule: the same bits.  One wave per prompt, four per workgroup;
-// the prompt's two chains are read ONCE into registers (two indices per lane and trie) and judged once, then the wave walks
-// blockIdx.y's chunks of GRID_CHUNK combinations, GRID_FLIGHT at a time: their loads are all issued before the first reduction.
-// A prompt score_chains_pair_kernel refuses gets four NaN in every combination, a combination with an entry outside [0, G1) x
-// [0, G2) four NaN for every prompt; every index is checked before the load it is used in.
+// entry of each, and out[c][p][0..3] is what score_chains_pair_kernel writes for prompt p on those two entries — the same bits,
+// because both reduce through chain_lane, chain_wave and chain_write.  One wave per prompt, four per workgroup; the prompt's two
+// chains are read ONCE into registers (two indices per lane and trie) and judged once, then the wave walks blockIdx.y's chunks of
+// GRID_CHUNK combinations, GRID_FLIGHT at a time: their loads are all issued before the first reduction.  A prompt
+// score_chains_pair_kernel refuses gets four NaN in every combination, a combination with an entry outside [0, G1) x [0, G2)
+// four NaN for every prompt.
 __global__ __launch_bounds__(256) void score_chains_pair_grid_kernel(
     const double* __restrict__ node1, int64_t G1, int64_t U1, const int32_t* __restrict__ anc1, int64_t ld_anc1,
     const int32_t* __restrict__ depth1, const int64_t* __restrict__ end1, const double* __restrict__ node2, int64_t G2, int64_t U2,
@@ -318,31 +328,15 @@ __global__ __launch_bounds__(256) void score_chains_pair_grid_kernel(
     const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (p >= B) return;
     const int64_t e1 = end1[p], e2 = end2[p];
-    const bool e_ok = e1 >= 0 && e1 < U1 && e2 >= 0 && e2 < U2;
-    const int n = e_ok ? depth1[e1] + 1 : 0, n2 = e_ok ? depth2[e2] + 1 : 0;
-    bool ok = e_ok && n == n2 && n >= 1 && n <= 128 && n <= ld_anc1 && n <= ld_anc2;
-    int64_t u1[2] = {0, 0}, u2[2] = {0, 0};        // the lane's two chain positions in each trie
-    bool take[2] = {false, false};
-    if (ok) {
-        const int32_t* c1 = anc1 + e1 * ld_anc1;
-        const int32_t* c2 = anc2 + e2 * ld_anc2;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int pos = lane + 64 * j;
-            if (pos < n) {
-                const int64_t a = c1[pos], b = c2[pos];
-                if (a < 0 || a >= U1 || b < 0 || b >= U2) {
-                    ok = false;
-                } else {
-                    u1[j] = a;
-                    u2[j] = b;
-                    take[j] = true;
-                }
-            }
-        }
-    }
+    const bool e_ok = in_range(e1, U1) && in_range(e2, U2);
+    const int na = chain_admit(e_ok, e1, depth1, ld_anc1), nb = chain_admit(e_ok, e2, depth2, ld_anc2);
+    const int n = na == nb ? na : 0;
+    int64_t u1[2], u2[2];        // the lane's two chain positions in each trie
+    const bool ok1 = chain_entries(anc1, e1, ld_anc1, U1, n, lane, u1), ok2 = chain_entries(anc2, e2, ld_anc2, U2, n, lane, u2);
+    const bool ok = ok1 && ok2 && n >= 1;
+    const bool take[2] = {ok && lane < n, ok && lane + 64 < n};
     const int bad = __any(!ok);
-    const double nan = __longlong_as_double(0x7ff8000000000000LL);
+    const ChainAcc none = {};
     const int64_t n_chunks = (C + GRID_CHUNK - 1) / GRID_CHUNK;
     for (int64_t chunk = blockIdx.y; chunk < n_chunks; chunk += gridDim.y) {
         const int64_t c_end = (chunk + 1) * GRID_CHUNK < C ? (chunk + 1) * GRID_CHUNK : C;
@@ -354,7 +348,7 @@ __global__ __launch_bounds__(256) void score_chains_pair_grid_kernel(
                 live[k] = false;
                 if (c0 + k < c_end) {
                     const int64_t g1 = combo[2 * (c0 + k)], g2 = combo[2 * (c0 + k) + 1];
-                    live[k] = !bad && g1 >= 0 && g1 < G1 && g2 >= 0 && g2 < G2;
+                    live[k] = !bad && in_range(g1, G1) && in_range(g2, G2);
                     if (live[k]) {
                         const double* b1 = node1 + g1 * U1 * 8;
                         const double* b2 = node2 + g2 * U2 * 8;
@@ -371,45 +365,14 @@ __global__ __launch_bounds__(256) void score_chains_pair_grid_kernel(
 #pragma unroll
             for (int k = 0; k < GRID_FLIGHT; ++k) {
                 if (c0 + k >= c_end) break;
-                double2* o = reinterpret_cast<double2*>(out + ((c0 + k) * B + p) * 4);
+                double* o = out + ((c0 + k) * B + p) * 4;
                 if (!live[k]) {
-                    if (lane == 0) {
-                        o[0] = make_double2(nan, nan);
-                        o[1] = make_double2(nan, nan);
-                    }
+                    chain_write(o, lane, true, none, n);
                     continue;
                 }
-                double best = -1.0, sum = 0.0, last = 0.0;
-                int best_pos = 1 << 30;
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const int pos = lane + 64 * j;
-                    if (take[j]) {
-                        const double num = v1[k][j].x + v2[k][j].x, den = v1[k][j].y + v2[k][j].y;
-                        const double r = (num == 0.0 && den == 0.0) ? 0.0 : sqrt(num / den);
-                        sum += r;
-                        if (r > best) {
-                            best = r;
-                            best_pos = pos;
-                        }
-                        if (pos == n - 1) last = r;
-                    }
-                }
-#pragma unroll
-                for (int s = 32; s > 0; s >>= 1) {
-                    sum += __shfl_xor(sum, s, 64);
-                    last += __shfl_xor(last, s, 64);
-                    const double ob = __shfl_xor(best, s, 64);
-                    const int op = __shfl_xor(best_pos, s, 64);
-                    if (ob > best || (ob == best && op < best_pos)) {
-                        best = ob;
-                        best_pos = op;
-                    }
-                }
-                if (lane == 0) {
-                    o[0] = make_double2(best, sum / (double)n);
-                    o[1] = make_double2(last, (double)best_pos);
-                }
+                ChainAcc a = chain_lane(take, lane, n, [&](int j) { return make_double2(v1[k][j].x + v2[k][j].x, v1[k][j].y + v2[k][j].y); });
+                chain_wave(a);
+                chain_write(o, lane, false, a, n);
             }
         }
     }

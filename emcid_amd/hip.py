@@ -1742,6 +1742,15 @@ def session_step_norms(ws: PreserveWorkspace, N: int, d: int, h: int, state: Pre
 SCORE_MAX_COLS = 2048
 
 
+def _f64_out(who: str, out: Optional[torch.Tensor], shape: tuple, device) -> torch.Tensor:
+    """``out`` when it is a contiguous f64 tensor of ``shape`` on ``device`` (refused otherwise), a new one for ``None``."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float64, device=device)
+    if out.dtype != torch.float64 or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != device:
+        raise EmcidHipError(f"{who}: out must be a contiguous ({', '.join(str(n) for n in shape)}) f64 tensor on {device}")
+    return out
+
+
 def score_rows(a: torch.Tensor, b: torch.Tensor, t: Optional[torch.Tensor] = None, ln: Optional[torch.nn.LayerNorm] = None,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(rows, 8) f64 in HBM, one launch (include/emcid_hip.h, emcid_score_rows_f32): per row of the fp32 matrices ``a``, ``b``
@@ -1759,10 +1768,7 @@ def score_rows(a: torch.Tensor, b: torch.Tensor, t: Optional[torch.Tensor] = Non
     if ln is not None and (ln.weight is None or ln.bias is None or tuple(ln.normalized_shape) != (cols,)
                            or not ln.weight.is_contiguous() or not ln.bias.is_contiguous()):
         raise EmcidHipError("score_rows: a LayerNorm over the last dimension with contiguous affine parameters")
-    if out is None:
-        out = torch.empty(rows, 8, dtype=torch.float64, device=a.device)
-    if out.dtype != torch.float64 or tuple(out.shape) != (rows, 8) or not out.is_contiguous() or out.device != a.device:
-        raise EmcidHipError(f"score_rows: out must be a contiguous ({rows}, 8) f64 tensor on {a.device}")
+    out = _f64_out("score_rows", out, (rows, 8), a.device)
     _check(load().emcid_score_rows_f32(
         _ptr(a, torch.float32, "a"), a.stride(0), _ptr(b, torch.float32, "b"), b.stride(0), _ptr(t, torch.float32, "t"),
         t.stride(0) if t is not None else 0, _ptr(ln.weight, torch.float32, "gamma") if ln is not None else None,
@@ -1782,6 +1788,19 @@ def _check_chain_arrays(who: str, node: torch.Tensor, anc: torch.Tensor, depth: 
         raise EmcidHipError(f"{who}: end_node must be a non-empty contiguous (B,) int64 tensor")
 
 
+def _check_chain_pair(who: str, first: tuple, second: tuple, more: tuple = ()) -> int:
+    """The pairing of two tries' (node, anc, depth, end_node): each as ``_check_chain_arrays`` takes it, as many end nodes in one
+    as in the other, and they and ``more`` on one device.  Returns that number B of end nodes."""
+    _check_chain_arrays(who, *first)
+    _check_chain_arrays(who, *second)
+    B = first[3].numel()
+    if second[3].numel() != B:
+        raise EmcidHipError(f"{who}: {B} end nodes in the first trie, {second[3].numel()} in the second")
+    if any(x.device != first[0].device for x in first[1:] + second + more):
+        raise EmcidHipError(f"{who}: every operand must live on {first[0].device}")
+    return B
+
+
 def score_chains(node: torch.Tensor, anc: torch.Tensor, depth: torch.Tensor, end_node: torch.Tensor,
                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """(B, 4) f64 in HBM, one launch (emcid_score_chains_f64): per prompt the max, the mean and the end-node value of
@@ -1793,10 +1812,7 @@ def score_chains(node: torch.Tensor, anc: torch.Tensor, depth: torch.Tensor, end
     if any(x.device != node.device for x in (anc, depth, end_node)):
         raise EmcidHipError(f"score_chains: every operand must live on {node.device}")
     B = end_node.numel()
-    if out is None:
-        out = torch.empty(B, 4, dtype=torch.float64, device=node.device)
-    if out.dtype != torch.float64 or tuple(out.shape) != (B, 4) or not out.is_contiguous() or out.device != node.device:
-        raise EmcidHipError(f"score_chains: out must be a contiguous ({B}, 4) f64 tensor on {node.device}")
+    out = _f64_out("score_chains", out, (B, 4), node.device)
     _check(load().emcid_score_chains_f64(
         _ptr(node, torch.float64, "node"), U, _ptr(anc, torch.int32, "anc"), anc.stride(0), _ptr(depth, torch.int32, "depth"),
         _ptr(end_node, torch.int64, "end_node"), B, _ptr(out, torch.float64, "out"), _stream(node)), "emcid_score_chains_f64")
@@ -1810,17 +1826,8 @@ def score_chains_pair(node1: torch.Tensor, anc1: torch.Tensor, depth1: torch.Ten
     Per prompt p and chain position j, with c_e the chain ``anc_e[end_node_e[p], 0 .. depth_e[end_node_e[p]]]`` in encoder e's own
     trie, r_j = sqrt((node1[c_1[j], 0] + node2[c_2[j], 0]) / (node1[c_1[j], 1] + node2[c_2[j], 1])); the max, the mean, the value at
     the end and the chain position of the max.  A prompt whose two chains differ in length (or leave their tries) gets four NaN."""
-    _check_chain_arrays("score_chains_pair", node1, anc1, depth1, end_node1)
-    _check_chain_arrays("score_chains_pair", node2, anc2, depth2, end_node2)
-    B = end_node1.numel()
-    if end_node2.numel() != B:
-        raise EmcidHipError(f"score_chains_pair: {B} end nodes in the first trie, {end_node2.numel()} in the second")
-    if any(x.device != node1.device for x in (anc1, depth1, end_node1, node2, anc2, depth2, end_node2)):
-        raise EmcidHipError(f"score_chains_pair: every operand must live on {node1.device}")
-    if out is None:
-        out = torch.empty(B, 4, dtype=torch.float64, device=node1.device)
-    if out.dtype != torch.float64 or tuple(out.shape) != (B, 4) or not out.is_contiguous() or out.device != node1.device:
-        raise EmcidHipError(f"score_chains_pair: out must be a contiguous ({B}, 4) f64 tensor on {node1.device}")
+    B = _check_chain_pair("score_chains_pair", (node1, anc1, depth1, end_node1), (node2, anc2, depth2, end_node2))
+    out = _f64_out("score_chains_pair", out, (B, 4), node1.device)
     _check(load().emcid_score_chains_pair_f64(
         _ptr(node1, torch.float64, "node1"), node1.shape[0], _ptr(anc1, torch.int32, "anc1"), anc1.stride(0),
         _ptr(depth1, torch.int32, "depth1"), _ptr(end_node1, torch.int64, "end_node1"),
@@ -1840,22 +1847,14 @@ def score_chains_pair_grid(node1_bank: torch.Tensor, anc1: torch.Tensor, depth1:
     for bank, nm in ((node1_bank, "node1_bank"), (node2_bank, "node2_bank")):
         if bank.dim() != 3 or bank.shape[0] < 1:
             raise EmcidHipError(f"score_chains_pair_grid: {nm} must be a (G, U, 8) f64 tensor (got {tuple(bank.shape)})")
-    _check_chain_arrays("score_chains_pair_grid", node1_bank[0], anc1, depth1, end_node1)
-    _check_chain_arrays("score_chains_pair_grid", node2_bank[0], anc2, depth2, end_node2)
     if not node1_bank.is_contiguous() or not node2_bank.is_contiguous():
         raise EmcidHipError("score_chains_pair_grid: the banks must be contiguous")
-    B = end_node1.numel()
-    if end_node2.numel() != B:
-        raise EmcidHipError(f"score_chains_pair_grid: {B} end nodes in the first trie, {end_node2.numel()} in the second")
     if combo.dim() != 2 or combo.shape[1] != 2 or combo.shape[0] < 1 or not combo.is_contiguous():
         raise EmcidHipError(f"score_chains_pair_grid: combo must be a non-empty contiguous (C, 2) int32 tensor (got {tuple(combo.shape)})")
-    if any(x.device != node1_bank.device for x in (anc1, depth1, end_node1, node2_bank, anc2, depth2, end_node2, combo)):
-        raise EmcidHipError(f"score_chains_pair_grid: every operand must live on {node1_bank.device}")
+    B = _check_chain_pair("score_chains_pair_grid", (node1_bank[0], anc1, depth1, end_node1), (node2_bank[0], anc2, depth2, end_node2),
+                          (combo,))
     n_combo = combo.shape[0]
-    if out is None:
-        out = torch.empty(n_combo, B, 4, dtype=torch.float64, device=node1_bank.device)
-    if out.dtype != torch.float64 or tuple(out.shape) != (n_combo, B, 4) or not out.is_contiguous() or out.device != node1_bank.device:
-        raise EmcidHipError(f"score_chains_pair_grid: out must be a contiguous ({n_combo}, {B}, 4) f64 tensor on {node1_bank.device}")
+    out = _f64_out("score_chains_pair_grid", out, (n_combo, B, 4), node1_bank.device)
     _check(load().emcid_score_chains_pair_grid_f64(
         _ptr(node1_bank, torch.float64, "node1_bank"), node1_bank.shape[0], node1_bank.shape[1], _ptr(anc1, torch.int32, "anc1"),
         anc1.stride(0), _ptr(depth1, torch.int32, "depth1"), _ptr(end_node1, torch.int64, "end_node1"),
@@ -1884,10 +1883,7 @@ def score_pooled(a: torch.Tensor, b: torch.Tensor, ln: torch.nn.LayerNorm, proj_
     if not isinstance(ln, torch.nn.LayerNorm) or ln.weight is None or ln.bias is None or tuple(ln.normalized_shape) != (cols,) \
             or not ln.weight.is_contiguous() or not ln.bias.is_contiguous() or ln.weight.device != a.device:
         raise EmcidHipError("score_pooled: a LayerNorm over the last dimension with contiguous affine parameters")
-    if out is None:
-        out = torch.empty(rows, 4, dtype=torch.float64, device=a.device)
-    if out.dtype != torch.float64 or tuple(out.shape) != (rows, 4) or not out.is_contiguous() or out.device != a.device:
-        raise EmcidHipError(f"score_pooled: out must be a contiguous ({rows}, 4) f64 tensor on {a.device}")
+    out = _f64_out("score_pooled", out, (rows, 4), a.device)
     _check(load().emcid_score_pooled_f32(
         _ptr(a, torch.float32, "a"), a.stride(0), _ptr(b, torch.float32, "b"), b.stride(0), _ptr(ln.weight, torch.float32, "gamma"),
         _ptr(ln.bias, torch.float32, "beta"), float(ln.eps), _ptr(proj_weight, torch.float32, "proj_weight"), proj_weight.stride(0),

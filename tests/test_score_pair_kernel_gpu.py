@@ -283,3 +283,33 @@ def test_pair_chains_bad_arguments_are_an_error_status_and_launch_nothing():
     assert bool(torch.isnan(out).all())
     with pytest.raises(hip.EmcidHipError, match="end nodes"):
         hip.score_chains_pair(out, anc, depth, ends, out, anc, depth, torch.zeros(2, dtype=torch.int64, device=DEV))
+
+
+@pytest.mark.parametrize("longest", [2, 65, 128])          # 65: one position in a lane's second slot; 128: both slots of every lane
+@pytest.mark.parametrize("B", [1, 5])
+def test_single_chains_have_the_bits_of_pair_chains_with_a_zero_second_encoder(B, longest):
+    """score_chains(node, ...) against score_chains_pair(node, ..., zeros_like(node) on the same trie, ...): the node sums are
+    non-negative, so x + 0.0 == x exactly, and both kernels reduce through the same helpers — the same bits, the position of the
+    max and the four NaN of a prompt whose end node is out of range included."""
+    rng = np.random.default_rng(100 * B + longest)
+    U = longest + 9
+    anc, depth = fr.random_trie(U, longest, rng)
+    node = rng.random((U, 8)) + 0.05
+    node[:, 0] *= rng.random(U) * 4.0
+    node[0] = 0.0                                           # the root: r = 0
+    node[longest - 1, :2] = node[longest // 2, :2] = (600.0, 0.125)          # the largest ratio twice along the longest chain
+    ends = ([longest - 1] + [int(x) for x in rng.integers(0, U, size=4)])[:B]
+    if B > 1:
+        ends[3] = U                                         # out of range: four NaN
+    node_d = torch.from_numpy(node).to(DEV)
+    trie = (anc.to(DEV), depth.to(DEV))
+    for end in [ends] + ([[U], [-1]] if B == 1 else []):
+        end_d = torch.tensor(end, dtype=torch.int64, device=DEV)
+        single = hip.score_chains(node_d, *trie, end_d)
+        pair = hip.score_chains_pair(node_d, *trie, end_d, torch.zeros_like(node_d), *trie, end_d)
+        torch.cuda.synchronize()
+        assert torch.equal(single.view(torch.int64), pair.view(torch.int64)), end
+        bad = torch.tensor([not 0 <= e < U for e in end])
+        assert bool(torch.isnan(single.cpu()[bad]).all()) and not bool(torch.isnan(single.cpu()[~bad]).any()), end
+        if not bad[0]:
+            assert float(single[0, 3]) == longest // 2 and float(single[0, 0]) == float(single[0, 2])       # the tie: its first position
