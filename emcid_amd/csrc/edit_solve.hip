@@ -702,6 +702,9 @@ int emcid_edit_dual_cols_stage2_f64(int64_t N, int64_t d, int64_t h, const void*
     double *Yc = base + ws.off_Y, *R = base + ws.off_R, *S = base + ws.off_S, *LS = base + ws.off_LS, *invS = base + ws.off_invS;
     double *RT = base + ws.off_PT, *Y2 = base + ws.off_Y2, *V = base + ws.off_V, *U = base + ws.off_U;
     const int64_t dp = ws.dp, Np = ws.Np, hp = ws.hp;
+    // (solve_schur_rhs refuses the same, but only behind add_identity and the factorization: outside a graph capture S would
+    // already be rewritten.  A refused call launches nothing.)
+    if (ws.y2_doubles() < hp * Np) return fail(EMCID_ERR_WORKSPACE, __func__, "RT / Y2 hold fewer than h rows of Np (h > d rounded up to 128)");
     const double* X = CovFactorLayout(n_layers, d).X(cov_factor_ws, layer_index);
     const int w = n_tiles * NB;
     const bool xrow = cholesky_takes_shadow(Np);

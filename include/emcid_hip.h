@@ -628,6 +628,9 @@ int emcid_lu_solve_f64(double* A, int64_t lda, int64_t n, double* B, int64_t ldb
  *     stage 2:  S + I = L_S L_S^T, Z = S^-1 Rt, V = Z^T Yc, partial U_r = V X[tiles, :] -> emcid_edit_dual_u() [hp][dp] f64
  *     caller :  all-reduce (sum) of U, then emcid_apply_update2d_f32 (W = W0 + float(U), ldu = dp)
  * Summed over the ranks this is exactly emcid_edit_dual_apply_stage1/2 (same algebra, sums in another order).
+ * Stage 2 reads the lower 128-tiles of the summed S only.  A bad tile list (empty, not ascending, an index outside
+ * [0, dp / 128), more than 256 tiles) is EMCID_ERR_BAD_ARG and h > dp (RT / Y2 hold dp rows) EMCID_ERR_WORKSPACE, both
+ * before anything is launched.
  * ------------------------------------------------------------------------------------------- */
 int emcid_edit_dual_cols_stage1_f64(const float* K, const float* Zc, const float* zs_t, int64_t N, int64_t d, int64_t h,
                                     double edit_weight, int layers_left, double lam_ratio, const void* cov_factor_ws, int64_t n_layers,
