@@ -300,8 +300,10 @@ int emcid_clip_edit_layer_tail_sp16(const emcid_clip_layer_sp16* L, int64_t n_ro
                                     float* x_inv_scale, void* stream) {
     EMCID_CHECK_ARG(L && n_rows > 0 && h % 32 == 0 && d % 32 == 0 && f_f32 && lookup && seg && B > 0 && N > 0 && zs_t);
     EMCID_CHECK_ARG(cov_factor_ws && W0 && W && K_out && Zc_out && dual_ws && info_dev && (hs_out == nullptr || (f_planes && f_inv_scale && mid)));
-    EMCID_TRY(emcid_gather_mean_f32(f_f32, B, n_rows, d, 0, d, lookup, seg, N, K_out, d, stream));
+    // (everything a later stage would refuse on the caller's arguments alone, before the first launch: a refused call has written nothing)
     EMCID_CHECK_ARG((k_planes == nullptr) == (k_inv_scale == nullptr));
+    EMCID_CHECK_WORKSPACE(dual_ws_bytes, emcid_edit_dual_workspace_bytes(N, d, h), " (see emcid_edit_dual_workspace_bytes)");
+    EMCID_TRY(emcid_gather_mean_f32(f_f32, B, n_rows, d, 0, d, lookup, seg, N, K_out, d, stream));
     if (k_planes != nullptr) {
         // Zc on the split-fp16 kernel against the layer's own fc2 planes (they are the planes of the CURRENT weight: the caller
         // splits a weight once per version, and this layer's has not been touched yet in this call)

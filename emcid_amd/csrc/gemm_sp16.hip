@@ -84,7 +84,7 @@ struct SpGeom {
     static constexpr int SMEM = 2 * STAGE > RED ? 2 * STAGE : RED;
 };
 
-template <int MJ, int NI, int WM, int WN, int PF, int DBG, int KS>
+template <int MJ, int NI, int WM, int WN, int PF, int DBG, int KS, bool SA = false>
 __device__ __forceinline__ void sp_accumulate(const SpArgs& a, int m0, int n0, int T, unsigned char* smem, v16f (&acc)[NI][MJ]) {
     using G = SpGeom<MJ, NI, WM, WN, PF, KS>;
     constexpr int NT = G::NT, BM = G::BM, BN = G::BN, VA = G::VA, VB = G::VB, STAGE = G::STAGE, PPR = G::PPR, SPROW = G::ROW,
@@ -152,18 +152,42 @@ __device__ __forceinline__ void sp_accumulate(const SpArgs& a, int m0, int n0, i
             wl[slot][i] = *reinterpret_cast<const v8h*>(stage + fw_off + i * 32 * SPROW + 64 * t + 16);
         }
     };
+    // SA (one block per wave, a long K): every MFMA rounds the accumulator once, so the one accumulator of a few-tile launch over
+    // K = 3072 carries 576 roundings at its full magnitude — measured 1.3e-6 to 1.6e-6 of the largest output on fc2 of N <= 130 keys
+    // at d = 3072, 4 to 5 times the plain fp32 formula, where the planes themselves are good to 7e-8.  With SA the two small products
+    // go to an accumulator of their own (2^-11 of the magnitude) and hi x hi alternates between two by the k16 step of its stage:
+    // 96 roundings each at half the magnitude (4.4e-7 to 5.5e-7 on the same inputs); the three are added once at the end, in a
+    // fixed order.  The dispatcher takes it from K = 2048 on: on the K = 768 launches of a forward it gains nothing and bench.py
+    // read 1 to 3 % more per call with it everywhere.
+    constexpr bool SPLIT_ACC = SA && MJ * NI == 1;
+    v16f acc_small, acc_odd;
+    if constexpr (SPLIT_ACC) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc_small[r] = 0.f, acc_odd[r] = 0.f;
+    }
     // the two small products first, then hi x hi; p selects the product so that the three MFMAs of one accumulator are a
     // block apart in the issue order
     auto mfmas = [&](int slot, int p_lo, int p_hi) __attribute__((always_inline)) {
 #pragma unroll
         for (int p = 0; p < 3; ++p)
-            if (p >= p_lo && p < p_hi)
+            if (p >= p_lo && p < p_hi) {
+                if constexpr (SPLIT_ACC) {
+                    if (p < 2)
+                        acc_small = __builtin_amdgcn_mfma_f32_32x32x16_f16(p == 0 ? wl[slot][0] : wh[slot][0],
+                                                                           p == 1 ? xl[slot][0] : xh[slot][0], acc_small, 0, 0, 0);
+                    else if (slot == 0)
+                        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[slot][0], xh[slot][0], acc[0][0], 0, 0, 0);
+                    else
+                        acc_odd = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[slot][0], xh[slot][0], acc_odd, 0, 0, 0);
+                } else {
 #pragma unroll
-                for (int i = 0; i < NI; ++i)
+                    for (int i = 0; i < NI; ++i)
 #pragma unroll
-                    for (int j = 0; j < MJ; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p == 0 ? wl[slot][i] : wh[slot][i],
-                                                                           p == 1 ? xl[slot][j] : xh[slot][j], acc[i][j], 0, 0, 0);
+                        for (int j = 0; j < MJ; ++j)
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(p == 0 ? wl[slot][i] : wh[slot][i],
+                                                                               p == 1 ? xl[slot][j] : xh[slot][j], acc[i][j], 0, 0, 0);
+                }
+            }
     };
 
     // Everything inside the loop is unconditional — past the end the loads re-fetch the last stage and the LDS writes / fragment
@@ -220,6 +244,10 @@ __device__ __forceinline__ void sp_accumulate(const SpArgs& a, int m0, int n0, i
             body(SpIC<0>{}, it + 1);
         }
         if (it < T) body(SpIC<1>{}, it);
+    }
+    if constexpr (SPLIT_ACC) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[0][0][r] = (acc[0][0][r] + acc_odd[r]) + acc_small[r];
     }
 }
 
@@ -372,7 +400,7 @@ __device__ __forceinline__ void sp_finish(const SpArgs& a, int m0, int n0, unsig
     else epilogue([](float x) { return x; });
 }
 
-template <int MJ, int NI, int WM, int WN, int PF, int WPE, int DBG, int KS>
+template <int MJ, int NI, int WM, int WN, int PF, int WPE, int DBG, int KS, bool SA = false>
 __global__ __launch_bounds__(64 * WM * WN * KS) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 void linear_sp16_kernel(SpArgs a) {
     using G = SpGeom<MJ, NI, WM, WN, PF, KS>;
@@ -390,7 +418,7 @@ void linear_sp16_kernel(SpArgs a) {
         for (int j = 0; j < MJ; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    sp_accumulate<MJ, NI, WM, WN, PF, DBG, KS>(a, bm * G::BM, bn * G::BN, a.K / G::SBK, smem, acc);
+    sp_accumulate<MJ, NI, WM, WN, PF, DBG, KS, SA>(a, bm * G::BM, bn * G::BN, a.K / G::SBK, smem, acc);
     sp_finish<MJ, NI, WM, WN, KS>(a, bm * G::BM, bn * G::BN, smem, acc);
 }
 
@@ -993,7 +1021,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 
 struct SpCfg { int bm, bn; };
-static const SpCfg kSpCfgs[] = {{128, 128}, {80, 128}, {64, 64}, {160, 128}, {64, 64}};
+static const SpCfg kSpCfgs[] = {{128, 128}, {80, 128}, {64, 64}, {160, 128}, {64, 64}, {64, 64}};
 inline long long* g_sp16_stamps = nullptr;      // set by emcid_debug_linear_sp16_stamps
 
 }  // namespace emcid
@@ -1083,12 +1111,13 @@ int emcid_linear_sp16_f32(const void* Xp, int64_t ldx, const float* x_inv_scale,
     // cfg: -1 auto; 0: 128 x 128 (two waves by two, 64 x 64 each, both fragment sets in registers); 1: 80 x 128 (four waves side
     // by side, 80 x 32 each); 2: 64 x 64 (four workgroups per compute unit); 3: 160 x 128 (80 x 64 per wave, fragments reloaded
     // progressively) — all four: operands by LDS-DMA, v_mfma_f32_16x16x32_f16, epilogue through LDS —; 4: 64 x 64 with
-    // register-staged operands on v_mfma_f32_32x32x16_f16, two stages of loads in flight (latency-bound launches); + 16 / + 48
+    // register-staged operands on v_mfma_f32_32x32x16_f16, two stages of loads in flight (latency-bound launches);
+    // 5: form 4 with its sum over three accumulators (sp_accumulate, SA), what -1 takes in form 4's place from K = 2048 on; + 16 / + 48
     // with cfg 0: timing-only builds (no DMA inside the loop / MFMAs only; results wrong).
     EMCID_CHECK_ARG(ldx < (1 << 20) && ldw < (1 << 20));      // 32-bit buffer offsets of a tile's rows
     const int dbg = cfg < 0 ? 0 : (cfg >> 4) & 3;
     int tile_sel = cfg < 0 ? -1 : (cfg & 15);
-    EMCID_CHECK_ARG(tile_sel <= 4 && (dbg == 0 || tile_sel == 0) && dbg != 2);
+    EMCID_CHECK_ARG(tile_sel <= 5 && (dbg == 0 || tile_sel == 0) && dbg != 2);
     if (tile_sel < 0) {
         // profiles/r05_mb_linear_sp16_forms.txt, r05_mb_linear_sp16_small.txt (six LDS-DMA forms and the register-staged ones on
         // 27 shapes, interleaved rounds in one process).  The largest of 128 x 128, 80 x 128, 64 x 64 that still gives ~400
@@ -1103,7 +1132,7 @@ int emcid_linear_sp16_f32(const void* Xp, int64_t ldx, const float* x_inv_scale,
         else if (t128 >= 400) tile_sel = 0;
         else if (t80 >= 400) tile_sel = 1;
         else if (t64 >= 256) tile_sel = 2;
-        else tile_sel = 4;
+        else tile_sel = K >= 2048 ? 5 : 4;
     }
     const int bm = kSpCfgs[tile_sel].bm, bn = kSpCfgs[tile_sel].bn;
     const int tiles_m = (int)((M + bm - 1) / bm), tiles_n = (int)((N + bn - 1) / bn);
@@ -1126,6 +1155,9 @@ int emcid_linear_sp16_f32(const void* Xp, int64_t ldx, const float* x_inv_scale,
         case 1: EMCID_SP_DMA16(5, 2, 1, 4, 2, 2, 0); break;
         case 2: EMCID_SP_DMA16(2, 2, 2, 2, 2, 4, 0); break;      // 32 KB of LDS, 128 registers: four workgroups per compute unit
         case 3: EMCID_SP_DMA16(5, 4, 2, 2, 1, 2, 0); break;      // (two fragment sets would spill: 56 registers)
+        case 5:
+            hipLaunchKernelGGL((linear_sp16_kernel<1, 1, 2, 2, 2, 4, 0, 1, true>), dim3((unsigned)(per * 8)), dim3(256), 0, st, a);
+            break;
         default:
             hipLaunchKernelGGL((linear_sp16_kernel<1, 1, 2, 2, 2, 4, 0, 1>), dim3((unsigned)(per * 8)), dim3(256), 0, st, a);
             break;

@@ -135,7 +135,8 @@ int emcid_split_rows_f16(const float* X, int64_t ldx, int64_t rows, int64_t K, v
  * 128 x 128 tiles, 1: 80 x 128, 2: 64 x 64, 3: 160 x 128 — four waves, operands by LDS-DMA (buffer_load ... lds into an
  * XOR-swizzled image, no staging registers, no LDS stores), three v_mfma_f32_16x16x32_f16 per k-step and accumulator block,
  * epilogue through LDS (whole-row stores); 4: 64 x 64 with register-staged operands on v_mfma_f32_32x32x16_f16 (launches of less
- * than one tile per compute unit); + 16 / + 48 with cfg 0: timing-only builds (results wrong).  The forms sum in different
+ * than one tile per compute unit), 5: form 4 with the sum kept in three accumulators (the small products; hi x hi of the even and
+ * of the odd k16 steps), which -1 takes in form 4's place from K = 2048 on; + 16 / + 48 with cfg 0: timing-only builds (results wrong).  The forms sum in different
  * orders: compare, do not equate. */
 int emcid_linear_sp16_f32(const void* Xp, int64_t ldx, const float* x_inv_scale, const void* Wp, int64_t ldw,
                           const float* w_inv_scale, const float* bias, const float* residual, int64_t ldr, float* Y, int64_t ldy,

@@ -134,6 +134,45 @@ def clip_layer_ref(weights: dict, hs, anc, depth, rows_sel=None, dtype=torch.flo
     return mid, f, lin(f, weights["fc2"]) + mid
 
 
+def request_means(rows, lookup, seg, dtype=torch.float64) -> torch.Tensor:
+    """Per-request mean of rows[lookup[seg[i] : seg[i + 1]]] in ``dtype`` (torch's stack(...).mean(0), like the reference)."""
+    rows, lookup, seg = rows.detach().cpu().to(dtype), lookup.cpu().long(), seg.cpu().long()
+    picked = rows[lookup]
+    return torch.stack([picked[int(seg[i]):int(seg[i + 1])].mean(0) for i in range(seg.numel() - 1)])
+
+
+def edited_layer_ref(f, mid, lookup, seg, W, b2, zs_t, Cov, lam: float, edit_weight: float, layers_left: int, next_ln=None,
+                     dtype=torch.float64):
+    """The body of the reference's sequential layer loop behind ``clip_layer_ref``'s (mid, f): the keys K = per-request means of
+    f's lookup rows, the current values Zc = K W^T + b2, the closed form U on those K and Zc (the oracle's fp64 LU:
+    ``closed_form_layer``; Cov stays fp32, the reference rounds C' there), W_new = W + float(U), fc2 + residual WITH THE NEW
+    WEIGHT, hs_out = f W_new^T + b2 + mid, and the next layer's LN1 of that.  ``zs_t`` (N, h): the targets; ``next_ln``:
+    (gamma, beta, eps) or None.  Returns (K, Zc, U, hs_out, x_next) — U in fp64, everything else in ``dtype``."""
+    from oracle import emcid_oracle as orc
+    t = lambda x: x.detach().cpu().to(dtype)
+    f, mid, W, b2 = t(f), t(mid), t(W), t(b2)
+    K = request_means(f, lookup, seg, dtype)
+    Zc = K @ W.T + b2
+    _, _, U = orc.closed_form_layer(K, Zc, zs_t.detach().cpu().t(), Cov.detach().cpu().float(), lam, edit_weight, layers_left)
+    W_new = W + U.float().to(dtype)
+    hs_out = f @ W_new.T + b2 + mid
+    x_next = None
+    if next_ln is not None:
+        g, b, eps = next_ln
+        x_next = F.layer_norm(hs_out, (hs_out.shape[1],), t(g), t(b), eps)
+    return K, Zc, U, hs_out, x_next
+
+
+def chain_trie(B: int, S: int):
+    """(anc (B S, S) int32, depth (B S,) int32) of B dense prompts of S tokens as a trie that shares nothing: node b S + s is
+    token s of prompt b and its chain is the prompt's tokens 0 .. s — causal attention inside the prompt."""
+    anc = torch.zeros(B * S, S, dtype=torch.int32)
+    for b in range(B):
+        for s in range(S):
+            anc[b * S + s, :s + 1] = torch.arange(b * S, b * S + s + 1, dtype=torch.int32)
+    return anc, torch.arange(S, dtype=torch.int32).repeat(B)
+
+
 def quick_gelu_ref(x: torch.Tensor) -> torch.Tensor:
     """x sigmoid(1.702 x) in fp64, rounded to fp32.  1.702 is the fp32 constant the kernel multiplies by."""
     xd = x.detach().cpu().double()
